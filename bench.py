@@ -19,6 +19,15 @@ scaling).  Every update all-gathers the 256-cell merit partials (the
 scheduler's global total, cMultiProcessWorld.cc:375-405) and exchanges
 occupancy / placement claims / offspring across strip edges
 (avida_amd/tiles.py), so the N-GPU run is cell for cell the untiled world.
+
+A plain run does what the headline figure needs and no more: it builds the
+world, ages and warms it, times the K updates and prints the line.  --full
+adds everything else the benchmark measures: the CPU baseline, the rooflines
+from the event-timed class-0 launches, the long run and the run with the
+statistics reduction every update; its timed updates are the plain run's.
+--dump-outputs DIR writes the world the last timed update left (what a caller
+of avgpu_run_update reads back through the inspection entry points) as .npy
+arrays, so that two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -45,7 +54,13 @@ HBM_PEAK_GBS = 8000.0         # MI355X_MICROARCH.md chip table (spec)
 BURN_IN = 150
 WARMUP = 5
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_k_interpret320.json")
-
+# --dump-outputs: per-cell census of at most this many cells (every cell of the
+# default world), whole state records and tapes of DUMP_BLOCKS runs of
+# DUMP_BLOCK_CELLS consecutive cells; a larger world is sampled with a fixed seed
+DUMP_CELLS = 1 << 20
+DUMP_BLOCKS = 8
+DUMP_BLOCK_CELLS = 64
+DUMP_SEED = 20240229
 
 
 def issue_roofline(cnt, c0_ms, c0_insts):
@@ -211,6 +226,76 @@ def cpu_baseline_multi(golden, seconds, env_kind, procs):
             "updates_per_sec": sum(o["updates_per_sec"] for o in outs)}
 
 
+STATS_INT_FIELDS = ["update", "num_organisms", "insts_executed", "births", "births_dropped", "deaths",
+                    "divides", "cum_insts_executed", "cum_births", "births_overwritten", "insts_wasted"]
+STATS_F64_FIELDS = ["sum_merit", "sum_fitness", "sum_gestation", "sum_genome_length", "max_fitness",
+                    "ave_generation", "sum_mem_size"]
+CENSUS_INT_FIELDS = ["genome_length", "gestation_time", "copied_size", "executed_size", "generation",
+                     "num_divides"]
+
+
+def _state_row(s):
+    """the architectural and phenotype scalars of one avgpu_cpu_state as floats
+    (every integer field is 32 bits wide, exact in float64)"""
+    row = list(s.reg) + list(s.head) + list(s.stack_ptr) + [s.cur_stack, s.mem_size, s.cpu_cycles_used,
+           s.time_used, s.gestation_start, s.gestation_time, s.num_divides, s.generation, s.alive,
+           s.genome_length, s.copied_size, s.child_copied_size, s.executed_size, s.max_executed,
+           s.birth_length, s.input_ptr, s.output_buf, s.errors, s.age]
+    row += list(s.input_buf) + list(s.inputs) + list(s.stack[0]) + list(s.stack[1])
+    row += list(s.cur_task_count) + list(s.last_task_count) + list(s.cur_reaction_count)
+    row += [s.cur_bonus, s.merit, s.fitness, s.credit]
+    return [float(v) for v in row]
+
+
+def dump_outputs(lib, capi, h, n, out_dir, suffix="", prefix="avgpu_"):
+    """What the last timed update left in the world, as a caller reads it back
+    (avgpu_get_stats, avgpu_get_census, avgpu_get_states; prefix "orc_": the
+    oracle's, for the CPU test of this layout), written as
+    out_dir/<name><suffix>.npy in float32 / float64 (under 64 MB in all):
+      stats        the update's statistics and cumulative counters
+      cells        the cell ids of the census rows below (every cell up to
+                   DUMP_CELLS of them, else a fixed seeded sample)
+      merit, fitness, census   per-cell census columns (CENSUS_INT_FIELDS)
+      state_cells, states, tape_ops, tape_flags   state records and memory
+                   tapes of DUMP_BLOCKS seeded runs of consecutive cells"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), arr)
+
+    st = capi.AvgpuUpdateStats()
+    capi.check(lib, getattr(lib, prefix + "get_stats")(h, C.byref(st)), prefix)
+    save("stats", np.array([float(getattr(st, f)) for f in STATS_INT_FIELDS + STATS_F64_FIELDS] +
+                           [float(v) for v in st.task_orgs], dtype=np.float64))
+    rng = np.random.default_rng(DUMP_SEED)
+    cells = np.arange(n, dtype=np.int64) if n <= DUMP_CELLS else \
+        np.sort(rng.choice(n, size=DUMP_CELLS, replace=False)).astype(np.int64)
+    census = capi.get_census(lib, prefix, h, 0, n)[cells]
+    save("cells", cells.astype(np.float64))
+    save("merit", census["merit"].astype(np.float64))
+    save("fitness", census["fitness"].astype(np.float64))
+    save("census", np.stack([census[f] for f in CENSUS_INT_FIELDS], axis=1).astype(np.float32))
+    nb = min(DUMP_BLOCKS, max(1, n // DUMP_BLOCK_CELLS))
+    bc = min(DUMP_BLOCK_CELLS, n)
+    starts = np.sort(rng.choice(max(1, n // bc), size=nb, replace=False)) * bc
+    cap = capi.MAX_GENOME
+    ids, rows, ops, flags = [], [], [], []
+    for first in (int(x) for x in starts):
+        ss = (capi.AvgpuCpuState * bc)()
+        o = (C.c_uint8 * (bc * cap))()
+        f = (C.c_uint8 * (bc * cap))()
+        capi.check(lib, getattr(lib, prefix + "get_states")(h, first, bc, ss, o, f, cap), prefix)
+        ids.extend(range(first, first + bc))
+        rows.extend(_state_row(x) for x in ss)
+        ops.append(np.frombuffer(o, dtype=np.uint8).reshape(bc, cap))
+        flags.append(np.frombuffer(f, dtype=np.uint8).reshape(bc, cap))
+    save("state_cells", np.array(ids, dtype=np.float64))
+    save("states", np.array(rows, dtype=np.float64))
+    save("tape_ops", np.concatenate(ops).astype(np.float32))
+    save("tape_flags", np.concatenate(flags).astype(np.float32))
+
+
 def free_port():
     import socket
     with socket.socket() as s:
@@ -255,9 +340,17 @@ def main():
                     help="untimed updates that age the seeded population before the warmup "
                          "(its organisms start in lock step; ~10 gestations spread them out)")
     ap.add_argument("--seed", type=int, default=101)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the timed steps, everything else the benchmark measures: the CPU "
+                         "baseline (--cpu-seconds, --cpu-procs, --no-cpu), the rooflines of the event-timed "
+                         "class-0 launches, the long run "
+                         "(--long-updates) and the run with statistics every update")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the world the last of them left (statistics, "
+                         "per-cell census, sampled state records and tapes) as DIR/<name>.npy")
     ap.add_argument("--time-every", type=int, default=4,
-                    help="bracket every k-th update's class-0 launch with HIP events (roofline timing; "
-                         "each event record leaves a few us of dead time on the stream)")
+                    help="bracket every k-th update's class-0 launch with HIP events (the roofline timing "
+                         "--full reports; each event record leaves a few us of dead time on the stream)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--env", choices=["logic9", "resources"], default="logic9",
@@ -282,7 +375,7 @@ def main():
         sys.exit(relaunch_ranks(args.gpus, sys.argv[1:]))
     rank, world, local = rank_env(args.gpus)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:   # before this process initialises the GPU
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:   # before this process initialises the GPU
         procs = args.cpu_procs or min(16, os.cpu_count() or 1)
         cpu = cpu_baseline_multi(golden, args.cpu_seconds, args.env, procs)
 
@@ -317,6 +410,7 @@ def main():
     transport = (tiles.StagedTransport(dist) if staged else tiles.DistTransport(dist)) if tile else None
     strips = tiles.StripWorld([tile], transport) if tile else None
 
+    # a plain run keeps the brackets too: its timed updates are --full's, launch for launch
     capi.check(lib, lib.avgpu_set_timing(h, args.time_every))
 
     def ref_insts():
@@ -388,8 +482,10 @@ def main():
                          dtype=torch.float64, device=rdev)
     if dist:
         dist.all_reduce(extra)
+    if args.dump_outputs:
+        dump_outputs(lib, capi, h, n, args.dump_outputs, f".rank{rank}" if world > 1 else "")
     long_run = None
-    if args.long_updates > 0:
+    if args.full and args.long_updates > 0:
         # stability cross-check outside the contract's timed region: the same
         # updates, many more of them, under the same barrier / max-over-ranks clock
         li0 = ref_insts()
@@ -411,7 +507,7 @@ def main():
         long_run = {"updates": args.long_updates, "value": lins.item() / ldt.item(),
                     "ms_per_step": ldt.item() * 1e3 / args.long_updates}
     stats_run = None
-    if args.long_updates > 0 and world == 1:
+    if args.full and args.long_updates > 0 and world == 1:
         # the timed updates skip the statistics reduction the reference runs
         # every update (cPopulation::UpdateOrganismStats, main/cPopulation.cc:6245;
         # DESIGN.md 5 "lazy statistics"): the same updates with it, stream-ordered
@@ -455,7 +551,7 @@ def main():
     bytes_per_launch = 2.0 * STATE_BYTES * c0_slices + SITE_BYTES * c0_sites
     achieved = bytes_per_launch / (c0_ms * 1e-3) / 1e9 if c0_ms > 0 else 0.0
     traffic, traffic_src, issue = None, None, None
-    if os.path.exists(PMC_FILE):
+    if args.full and os.path.exists(PMC_FILE):
         with open(PMC_FILE) as f:
             pmc = json.load(f)
         same_build = pmc.get("lib_sha16") == capi.lib_build_hash()
@@ -482,6 +578,7 @@ def main():
         "vs_baseline": None,
         "dtype": "int32",
         "data": "synthetic",
+        "full": args.full,
         "config": {
             "workload": (f"configs[2]: {args.side}x{args.side} torus per GPU, logic-9, default "
                          "avida.cfg mutation rates, births on, seeded with the detail-50000.pop "
@@ -517,7 +614,7 @@ def main():
         # (PMC wave-instructions per launch over the live event-timed launch);
         # the HBM roofline of the same launch (algorithmic bytes of SURVEY.md
         # 8(d) over the same duration, PMC traffic) follows as "hbm".
-        "roofline": {
+        "roofline": None if not args.full else {
             "bound": "issue",
             "binding": "VALU instruction issue + exposed LDS / memory latency",
             "achieved": issue["achieved"] if issue else None,
@@ -544,7 +641,7 @@ def main():
         },
         "cpu_baseline": None,
     }
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu
     lib.avgpu_destroy(h)
     print(json.dumps(out), flush=True)

@@ -3,12 +3,13 @@
 #   tools/gpu/ab.sh TAG V1 V2 ...   ("main" = the in-tree product library)
 set -o pipefail
 cd "$(dirname "$0")/../.."
-mkdir -p gpurun_out
+export OUT=${OUT:-bench_out}   # where the logs and results go
+mkdir -p "$OUT"
 TAG=$1; shift
 for V in "$@"; do
   if [ "$V" = main ]; then unset AVGPU_DIAG_LIB; else export AVGPU_DIAG_LIB=$PWD/avida_amd/libavida_gpu_$V.so; fi
-  timeout -k 10 300 python bench.py --steps 30 --warmup 5 --no-cpu --long-updates 100 > gpurun_out/ab_${TAG}_$V.log 2>&1 || { echo "bench $V failed"; tail -5 gpurun_out/ab_${TAG}_$V.log; exit 1; }
-  python - "$V" gpurun_out/ab_${TAG}_$V.log <<'PY'
+  timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --no-cpu --long-updates 100 > $OUT/ab_${TAG}_$V.log 2>&1 || { echo "bench $V failed"; tail -5 $OUT/ab_${TAG}_$V.log; exit 1; }
+  python - "$V" $OUT/ab_${TAG}_$V.log <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 r = d["roofline"]

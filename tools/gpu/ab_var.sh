@@ -4,7 +4,8 @@
 #   tools/gpu/ab_var.sh TAG main main:--time-every=4 lab,AVGPU_SLOW_BATCH=16
 set -o pipefail
 cd "$(dirname "$0")/../.."
-mkdir -p gpurun_out
+export OUT=${OUT:-bench_out}   # where the logs and results go
+mkdir -p "$OUT"
 TAG=$1; shift
 i=0
 for V in "$@"; do
@@ -14,9 +15,9 @@ for V in "$@"; do
   (
     if [ "$lib" = main ]; then unset AVGPU_DIAG_LIB; else export AVGPU_DIAG_LIB=$PWD/avida_amd/libavida_gpu_$lib.so; fi
     for e in ${envs//,/ }; do export "$e"; done
-    timeout -k 10 300 python bench.py --steps 30 --warmup 5 --no-cpu --long-updates 100 ${args//=/ } > gpurun_out/ab_${TAG}_$i.log 2>&1
-  ) || { echo "bench $V failed"; tail -5 gpurun_out/ab_${TAG}_$i.log; exit 1; }
-  python - "$V" gpurun_out/ab_${TAG}_$i.log <<'PY'
+    timeout -k 10 300 python bench.py --full --steps 30 --warmup 5 --no-cpu --long-updates 100 ${args//=/ } > $OUT/ab_${TAG}_$i.log 2>&1
+  ) || { echo "bench $V failed"; tail -5 $OUT/ab_${TAG}_$i.log; exit 1; }
+  python - "$V" $OUT/ab_${TAG}_$i.log <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 r = d["roofline"]
