@@ -291,6 +291,12 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   // 1.323 ms per update, profiles/r06g_ab_nbsb.txt)
   W.nb_slow_batch = 1;
   if (const char* e = getenv("AVGPU_NB_SLOW_BATCH")) W.nb_slow_batch = std::max(1, std::min(64, atoi(e)));
+  // the kernels that queue their IO task checks (interp.hip IOQ): IO, ~45 % of
+  // the bench population's parks, parks only on a full queue there, so the
+  // same wait fills half a batch (12 against 6 against 8 against 4:
+  // profiles/ioq_ab.txt)
+  W.ioq_slow_batch = 6;
+  if (const char* e = getenv("AVGPU_IOQ_SLOW_BATCH")) W.ioq_slow_batch = std::max(1, std::min(64, atoi(e)));
   W.row0 = 0;
   W.global_rows = c.world_y;
   W.rows = c.world_y;

@@ -207,6 +207,7 @@ struct DevWorld {
   uint8_t* rand_lut;  // [256] draw -> canonical code when rand_total <= 256
   int32_t slow_batch;   // parked lanes that trigger the interpreter's slow phase (1..64)
   int32_t nb_slow_batch;  // the same in the newborn pass
+  int32_t ioq_slow_batch; // the same in the main pass of the kernels that queue their IO task checks (interp.hip IOQ)
   int n_react;
   // reactions, RT_STRIDE words each: task, process type, requisite min / max
   // count, has-requisite, in-use, bonus multiplier (f64), bonus addend (f64)

@@ -219,6 +219,99 @@ __device__ __forceinline__ void res_flush(const DevWorld& W, const int64_t N, co
   }
 }
 
+// The simple environment's rewards without finite resources (reaction i
+// rewards task i, capi.hip avgpu_load_env): every lane applies its fired tasks
+// `done` -- the bonus factors multiply in reaction order (ascending bits), read
+// at a wave-uniform task (class 0: from ttab by v_readlane) -- and counts
+// them.  Runs with the wave converged.
+template <bool GTAB>
+__device__ __forceinline__ void simple_rewards(const uint32_t done, const uint32_t ttab, const double* tmul,
+                                               const double* tadd, int (&tc)[AVGPU_NUM_LOGIC_TASKS],
+                                               int (&rc)[AVGPU_MAX_REACTIONS], uint32_t& nzm, double& bonus) {
+  double mult = 1.0, addb = 0.0;
+  for (int t = 0; t < AVGPU_NUM_LOGIC_TASKS; t++) {   // wave-uniform t
+    const bool dt = (done >> t) & 1u;
+    if (__ballot(dt) == 0ull) continue;
+    const double fm = GTAB ? __hiloint2double(__builtin_amdgcn_readlane((int)ttab, 2 * t + 1),
+                                              __builtin_amdgcn_readlane((int)ttab, 2 * t)) : tmul[t];
+    const double fa = GTAB ? __hiloint2double(__builtin_amdgcn_readlane((int)ttab, 33 + 2 * t),
+                                              __builtin_amdgcn_readlane((int)ttab, 32 + 2 * t)) : tadd[t];
+    if (dt) { mult = __dmul_rn(mult, fm); addb = __dadd_rn(addb, fa); }
+  }
+  if (done) {
+#pragma unroll
+    for (int q = 0; q < AVGPU_NUM_LOGIC_TASKS; q++) {
+      tc[q] += (done >> q) & 1u;
+      rc[q] += (done >> q) & 1u;
+    }
+    nzm |= done;
+    bonus = __dadd_rn(__dmul_rn(bonus, mult), addb);   // cPhenotype.cc:1645-1646
+  }
+}
+
+// cTaskLib::SetupTests' logic id (main/cTaskLib.cc:395-440) of output o
+// against the input buffer's first num entries (in0 the newest), -1 for none:
+// per input combination p the output bits where the inputs spell p are all 1
+// (logic[p] = 1), all 0 (0), mixed (no id) or absent (-1); missing inputs
+// repeat the lower half; id = sum logic[p] 2^p.  In bit masks: "ones" /
+// "zeros" seen per p, present P = ones | zeros, and with every logic[p] in
+// {-1, 0, 1}, id = ones - (~P & 0xFF).  With three inputs and every
+// combination present -- always, for SetupInputs' 0x0F/0x33/0x55 top bytes --
+// that is just the "ones" mask.
+__device__ __forceinline__ int logic_id(const uint32_t o, const uint32_t in0, const uint32_t in1,
+                                        const uint32_t in2, const int num) {
+  const uint32_t a = num > 0 ? in0 : 0u;
+  const uint32_t b = num > 1 ? in1 : 0u;
+  const uint32_t c = num > 2 ? in2 : 0u;
+  uint32_t ones = 0u, zeros = 0u;
+#pragma unroll
+  for (int p = 0; p < 8; p++) {
+    const uint32_t m = ((p & 1) ? a : ~a) & ((p & 2) ? b : ~b) & ((p & 4) ? c : ~c);
+    ones |= min(o & m, 1u) << p;
+    zeros |= min(~o & m, 1u) << p;
+  }
+  // a missing input is 0, so the combinations that need it are absent and
+  // their bits are clear: the copies below only fill empty bits
+  uint32_t lo = ones, pr = ones | zeros;
+  if (num < 1) { lo |= (lo & 1u) << 1; pr |= (pr & 1u) << 1; }
+  if (num < 2) { lo |= (lo & 3u) << 2; pr |= (pr & 3u) << 2; }
+  if (num < 3) { lo |= (lo & 15u) << 4; pr |= (pr & 15u) << 4; }
+  const int id = (int)lo - (int)(~pr & 0xFFu);
+  return ((ones & zeros) == 0u && id >= 0) ? id : -1;
+}
+
+// interpret_chunk's queued IO task checks (IOQ there): the input buffer
+// (newest first) with input pointer pi after j inputs taken in this slice --
+// the cell's inputs inp0..inp2 in rotation back from the pointer, then the
+// staged buffer s0..s2
+__device__ __forceinline__ void io_hist(const int pi, const int j, const int inp0, const int inp1, const int inp2,
+                                        const int s0, const int s1, const int s2, int& a, int& b, int& c) {
+  const int n1 = pi == 1 ? inp0 : (pi == 2 ? inp1 : inp2);
+  const int n2 = pi == 1 ? inp2 : (pi == 2 ? inp0 : inp1);
+  const int n3 = pi == 1 ? inp1 : (pi == 2 ? inp2 : inp0);
+  a = j >= 1 ? n1 : s0;
+  b = j >= 2 ? n2 : (j == 1 ? s0 : s1);
+  c = j >= 3 ? n3 : (j == 2 ? s0 : (j == 1 ? s1 : s2));
+}
+// IO's immediate half for a lane whose queue has room (:4188 Inst_TaskIO):
+// DoOutput's buffer (q0), the queued check, GetNextInput + DoInput
+// (main/cOrganism.h:249 -> cPopulationCell.h:214-218) into register r
+__device__ __forceinline__ void io_now(const int r, int& r0, int& r1, int& r2, uint32_t& qm, int& q0, int& q1, int& q2,
+                                       int& intot, int& outtot, const int inp0, const int inp1, const int inp2) {
+  const int out = r == 0 ? r0 : (r == 1 ? r1 : r2);
+  outtot++;
+  const uint32_t top = qm >> 28, j = top >> 2;
+  const uint32_t code = (1u << 6) | ((uint32_t)min(intot, 3) << 4) | top;
+  q2 = q1; q1 = q0; q0 = out;
+  const uint32_t p = (top & 3u) == 3u ? 0u : (top & 3u);
+  const int in = p == 0u ? inp0 : (p == 1u ? inp1 : inp2);
+  qm = (((min(j + 1u, 3u) << 2) | (p + 1u)) << 28) | ((qm & 0x3FFFu) << 7) | code;
+  intot++;
+  r0 = r == 0 ? in : r0;
+  r1 = r == 1 ? in : r1;
+  r2 = (r != 0 && r != 1) ? in : r2;
+}
+
 __host__ __device__ constexpr int tape_stride(int S) { return S == CLASS0_SIZE ? S : S + 16; }
 
 // The adaptive sub-step predictor's term of one organism at the end of its
@@ -633,8 +726,32 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
   // slow switch only once W.slow_batch lanes are parked, or when no unparked
   // lane can step any more.  Each organism still executes its own
   // instructions in order -- only the interleaving across lanes changes.
-  int pop = -1, pr = 0;                                       // parked op, its register
-  int io_id = -2;                                             // IO's logic id (-1: none; -2: no IO this step)
+  int pop = -1;                                               // parked op | its register << 8
+  int io_id = -2;                                             // IO's logic id (-1: none; -2: no IO this step; !IOQ)
+  // IOQ (simple environment, no finite resource): an IO's task check updates
+  // only bonus, tc[], rc[] and nzm, which nothing reads before the lane's next
+  // check, its next divide or the slice's end.  So an IO does at once only
+  // what the organism sees -- its output, its next input -- in the branch-free
+  // part of the iteration, without parking, and queues the check as an event:
+  // the output value (q0 newest .. q2) and 7 bits of qm that name the input
+  // buffer at that moment (newest event in bits 0..6: bit 6 valid, bits 4..5
+  // min(inputs received, 3), bits 2..3 the inputs taken in this slice so far,
+  // capped at 3, bits 0..1 the input pointer).  The buffer's entries are then
+  // the cell's inputs in rotation back from the pointer, as many as this slice
+  // took, and after them the staged buffer in0..in2, which an IOQ kernel
+  // never rotates (the write-back rebuilds it the same way).  qm bits 28..31
+  // hold the running pair: the input pointer (an IOQ kernel keeps it nowhere
+  // else) and the inputs taken in this slice, capped at 3.  The output buffer
+  // is q0 once the slice has an IO (q0..q2 outlive their events), else the
+  // record's, read again at the write-back.  The wave evaluates the
+  // queued events together, each lane's in order (io_flush below): when a
+  // lane with a full queue parks on an IO, before a divide of a lane that has
+  // events, and once at the slice's end -- per lane the same arithmetic in the
+  // same order as a check at every IO.
+  constexpr bool IOQ = SIMPLE && !RES;
+  constexpr uint32_t IOQ_HAS = 1u << 6, IOQ_FULL = 1u << 20;   // depth 3
+  uint32_t qm = IOQ ? min((uint32_t)inptr, 3u) << 28 : 0u;
+  int q0 = 0, q1 = 0, q2 = 0;
   // class 0's task LUT (256 x u16) spread over the wave: lane j holds entries 4j .. 4j+3
   uint32_t tl0 = 0u, tl1 = 0u;
   // and its per-task bonus factors / addends (32 doubles): lane j holds word j,
@@ -647,12 +764,18 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     ttab = reinterpret_cast<const uint32_t*>(W.task_tab)[lane];
   }
   const uint32_t* T32 = reinterpret_cast<const uint32_t*>(T);
-  const int slow_batch = NB ? W.nb_slow_batch : W.slow_batch;
+  // (IOQ kernels have a threshold of their own: IO parks only on a full queue)
+  const int slow_batch = NB ? W.nb_slow_batch : (IOQ ? W.ioq_slow_batch : W.slow_batch);
   uint32_t rpq = 0u;        // configs[4]'s queued reward events (res_flush)
-
   while (true) {
     const bool run = fl == 0 && budget > 0 && pop < 0;
-    if (!__any(run || pop >= 0)) break;                       // wave-uniform loop
+    // (IOQ: when no lane can step any more, one last pass through the slow
+    // phase evaluates the events still queued)
+    bool fin = false;
+    if (!__any(run || pop >= 0)) {                            // wave-uniform loop
+      if (!IOQ || __ballot((qm & IOQ_HAS) != 0u) == 0ull) break;
+      fin = true;
+    }
 #ifdef AVGPU_PHASE_CLOCKS
     if (clast == 0) clast = __builtin_amdgcn_s_memtime();
     it_loop++;
@@ -858,7 +981,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     // inside the window (the copy loop's short labels): no park, no label
     // read.  The window holds sites ipa+1 .. ipa+avail; a label that may run
     // past them parks and reads its own 16-byte window in the slow phase.
-    bool lab_done = false;
+    bool inl_done = false;
     if (op == AVGPU_H_IF_LABEL && k_max_label_exe == 1) {
       const int base = ip + 1;
       const int avail = 7 - (ipa & 3);
@@ -868,7 +991,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
       const int run = nl ? (int)(__ffsll((long long)nl) - 8) >> 3 : 8;
       const int lim = min(AVGPU_MAX_LABEL, M - base);
       if (run < avail || lim <= avail) {
-        lab_done = true;
+        inl_done = true;
         const int len = max(min(run, lim), 0);
         uint64_t v = cl & 0x0303030303030303ull;
         v = (v | (v >> 6)) & 0x000F000F000F000Full;
@@ -883,8 +1006,13 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
         if (((uint32_t)len | (rot << 4)) != rl) ip = head_wrap(ip + 1, M);
       }
     }
+    // IO with room in the lane's event queue: no park
+    if (IOQ && op == AVGPU_H_IO && !(qm & IOQ_FULL)) {
+      inl_done = true;
+      io_now(r, r0, r1, r2, qm, q0, q1, q2, intot, outtot, inp0, inp1, inp2);
+    }
     CK(2);
-    if (!(FAST_OPS & obit) && op != AVGPU_H_H_COPY && !lab_done) { pop = op; pr = r; stepped = false; }   // park
+    if (!(FAST_OPS & obit) && op != AVGPU_H_H_COPY && !inl_done) { pop = op | (r << 8); stepped = false; }   // park
     }  // !spill
     }  // run
     if (stepped && !(fl & F_STOP)) {
@@ -896,7 +1024,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     }
     // ---- slow phase ----
     const int npark = __popcll(__ballot(pop >= 0));
-    if (npark == 0) continue;
+    if (npark == 0 && !fin) continue;
     if (npark < slow_batch && __any(fl == 0 && budget > 0 && pop < 0)) continue;
 #ifdef AVGPU_PHASE_CLOCKS
     it_slow++;
@@ -906,7 +1034,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     bool adv = true;
     const bool sstep = pop >= 0;
     if (sstep) {
-      const int op = pop, r = pr;
+      const int op = pop & 0xFF, r = pop >> 8;
       CKC(7);
       switch (op) {
       case AVGPU_H_POP:                                       // :2698, cCPUStack::Pop
@@ -940,40 +1068,16 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
         CKC(0);
         break; }
       case AVGPU_H_IO: {                                      // :4188 Inst_TaskIO
-        const int out = GETREG(r);
-        // cOrganism::DoOutput -> cTaskLib::SetupTests (main/cTaskLib.cc:369-448)
-        outv = out;
-        outtot++;
-        const int num = intot < 3 ? intot : 3;
-        const uint32_t a = num > 0 ? (uint32_t)in0 : 0u;
-        const uint32_t b = num > 1 ? (uint32_t)in1 : 0u;
-        const uint32_t c = num > 2 ? (uint32_t)in2 : 0u;
-        const uint32_t o = (uint32_t)out;
-        // logic id (cTaskLib::SetupTests, main/cTaskLib.cc:395-440): per input
-        // combination p the output bits where the inputs spell p are all 1
-        // (logic[p] = 1), all 0 (0), mixed (no id) or absent (-1); missing
-        // inputs repeat the lower half; id = sum logic[p] 2^p.  In bit masks:
-        // "ones" / "zeros" seen per p, present P = ones | zeros, and with
-        // every logic[p] in {-1, 0, 1}, id = ones - (~P & 0xFF).  With three
-        // inputs and every combination present -- always, for SetupInputs'
-        // 0x0F/0x33/0x55 top bytes -- that is just the "ones" mask.
-        uint32_t ones = 0u, zeros = 0u;
-#pragma unroll
-        for (int p = 0; p < 8; p++) {
-          const uint32_t m = ((p & 1) ? a : ~a) & ((p & 2) ? b : ~b) & ((p & 4) ? c : ~c);
-          ones |= min(o & m, 1u) << p;
-          zeros |= min(~o & m, 1u) << p;
+        // (IOQ: a lane whose event queue was full; its IO follows the flush below)
+        if (!IOQ) {
+          const int out = GETREG(r);
+          // cOrganism::DoOutput -> cTaskLib::SetupTests (main/cTaskLib.cc:369-448)
+          outv = out;
+          outtot++;
+          // the task lookup, the rewards and the input follow the switch, with
+          // the whole wave converged (io_id: the logic id, or -1 for none)
+          io_id = logic_id((uint32_t)out, (uint32_t)in0, (uint32_t)in1, (uint32_t)in2, intot < 3 ? intot : 3);
         }
-        // a missing input is 0, so the combinations that need it are absent
-        // and their bits are clear: the copies below only fill empty bits
-        uint32_t lo = ones, pr = ones | zeros;
-        if (num < 1) { lo |= (lo & 1u) << 1; pr |= (pr & 1u) << 1; }
-        if (num < 2) { lo |= (lo & 3u) << 2; pr |= (pr & 3u) << 2; }
-        if (num < 3) { lo |= (lo & 15u) << 4; pr |= (pr & 15u) << 4; }
-        const int id = (int)lo - (int)(~pr & 0xFFu);
-        // the task lookup, the rewards and the input follow the switch, with
-        // the whole wave converged (io_id: the logic id, or -1 for none)
-        io_id = ((ones & zeros) == 0u && id >= 0) ? id : -1;
         CKC(2);
         break; }
       case AVGPU_H_H_ALLOC: {                                 // :3294 Inst_MaxAlloc -> Allocate_Main :1707
@@ -1067,7 +1171,38 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     // bonus factors (ttab) by v_readlane at a wave-uniform task: a vector load
     // here waited (vmcnt) for every store the wave still had in flight, and a
     // scalar load per task present cost a memory round trip each.
-    if (__ballot(io_id >= -1) != 0ull) {
+    if (IOQ) {
+      // io_flush: while any lane has events, every lane evaluates its oldest
+      const bool iop = sstep && (pop & 0xFF) == AVGPU_H_IO;
+      if (fin || __ballot(iop || (rq == RQ_DIVIDE && (qm & IOQ_HAS) != 0u)) != 0ull) {
+        while (__ballot((qm & IOQ_HAS) != 0u) != 0ull) {
+          const uint32_t ev = qm & (2u * IOQ_FULL - 1u);
+          const int k = ev >= (IOQ_HAS << 8) ? 2 : (ev >= (IOQ_HAS << 1) ? 1 : 0);   // the oldest event's slot
+          const uint32_t code = (ev >> (7 * k)) & 127u;       // 0: the lane has none
+          const uint32_t o = (uint32_t)(k == 2 ? q2 : (k == 1 ? q1 : q0));
+          qm &= ~(127u << (7 * k));
+          int a, b, c;
+          io_hist((int)(code & 3u), (int)((code >> 2) & 3u), inp0, inp1, inp2, in0, in1, in2, a, b, c);
+          const int id = code ? logic_id(o, (uint32_t)a, (uint32_t)b, (uint32_t)c, (int)((code >> 4) & 3u)) : -1;
+          uint32_t tmask = 0u;
+          if (GLUT) {
+            const int sl = id >= 0 ? (id >> 2) : 0;
+            const uint32_t a0 = (uint32_t)__shfl((int)tl0, sl), a1 = (uint32_t)__shfl((int)tl1, sl);
+            const uint32_t wv = (id & 2) ? a1 : a0;
+            tmask = id >= 0 ? (wv >> ((id & 1) * 16)) & 0xFFFFu : 0u;
+          } else if (id >= 0) {
+            tmask = lut[id];
+          }
+          CKC(8);
+          // requisites at most "max_count=1": the firing set is a bit operation
+          const uint32_t done = tmask & k_env_react_mask & ~(k_env_once_mask & nzm);
+          if (__ballot(done != 0u) != 0ull) simple_rewards<GTAB>(done, ttab, tmul, tadd, tc, rc, nzm, bonus);
+          CKC(9);
+        }
+      }
+      // the parked IO, its queue now empty
+      if (iop) io_now(pop >> 8, r0, r1, r2, qm, q0, q1, q2, intot, outtot, inp0, inp1, inp2);
+    } else if (__ballot(io_id >= -1) != 0ull) {
       const bool io = io_id >= -1;
       uint32_t tmask = 0u;
       if (GLUT) {
@@ -1083,10 +1218,8 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
         // reaction i rewards task i, requisites at most "max_count=1"
         // (capi.hip avgpu_load_env): the firing set is a bit operation and
         // the bonus factors multiply in reaction order (ascending bits)
-        uint32_t done = io ? (tmask & k_env_react_mask & ~(k_env_once_mask & nzm)) : 0u;
+        const uint32_t done = io ? (tmask & k_env_react_mask & ~(k_env_once_mask & nzm)) : 0u;
         if (__ballot(done != 0u) != 0ull) {
-          double mult = 1.0, addb = 0.0;
-          uint32_t paid = done;
           if (k_env_res_mask != 0u) {
             // finite resources (configs[4]): the event is queued and its
             // bonus, reaction counts and consumption applied at the next
@@ -1102,27 +1235,8 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
               for (int q = 0; q < AVGPU_NUM_LOGIC_TASKS; q++) tc[q] += (done >> q) & 1u;
               nzm |= done;
             }
-            done = 0u;
-          } else
-          for (int t = 0; t < AVGPU_NUM_LOGIC_TASKS; t++) {   // wave-uniform t
-            const bool dt = (done >> t) & 1u;
-            if (__ballot(dt) == 0ull) continue;
-            {
-              const double fm = GTAB ? __hiloint2double(__builtin_amdgcn_readlane((int)ttab, 2 * t + 1),
-                                                        __builtin_amdgcn_readlane((int)ttab, 2 * t)) : tmul[t];
-              const double fa = GTAB ? __hiloint2double(__builtin_amdgcn_readlane((int)ttab, 33 + 2 * t),
-                                                        __builtin_amdgcn_readlane((int)ttab, 32 + 2 * t)) : tadd[t];
-              if (dt) { mult = __dmul_rn(mult, fm); addb = __dadd_rn(addb, fa); }
-            }
-          }
-          if (done) {
-#pragma unroll
-            for (int q = 0; q < AVGPU_NUM_LOGIC_TASKS; q++) {
-              tc[q] += (done >> q) & 1u;
-              rc[q] += (paid >> q) & 1u;
-            }
-            nzm |= done;
-            bonus = __dadd_rn(__dmul_rn(bonus, mult), addb);   // cPhenotype.cc:1645-1646
+          } else {
+            simple_rewards<GTAB>(done, ttab, tmul, tadd, tc, rc, nzm, bonus);
           }
         }
       } else if (io && tmask) {
@@ -1167,7 +1281,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
         inptr = p + 1;
         in2 = in1; in1 = in0; in0 = in;
         intot++;
-        SETREG(pr, in);
+        SETREG(pop >> 8, in);
       }
       io_id = -2;
     }
@@ -1880,6 +1994,16 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     // sectors of the cell's own lines)
     int4* xw = reinterpret_cast<int4*>(xrec);
     const long long bb = __double_as_longlong(bonus);
+    // IOQ: the input buffer after the slice's inputs (its event queue is empty)
+    if (IOQ) {
+      // (a slice without an IO leaves the record's pointer as it is)
+      inptr = (qm >> 30) ? (int)((qm >> 28) & 3u)
+                         : ((active && !fresh) ? *(volatile const int32_t*)(xrec + XS_INPTR) : 0);
+      int h0, h1, h2;
+      io_hist(inptr, (int)(qm >> 30), inp0, inp1, inp2, in0, in1, in2, h0, h1, h2);
+      in0 = h0; in1 = h1; in2 = h2;
+      outv = (qm >> 30) ? q0 : ((active && !fresh) ? *(volatile const int32_t*)(xrec + XS_OUTBUF) : 0);
+    }
     xw[0] = make_int4(r0, r1, r2, ip);
     xw[1] = make_int4(rh, wh, fh, (int)rl);
     xw[2] = make_int4(cyc, tu, gs, errs);
