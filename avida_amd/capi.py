@@ -185,6 +185,37 @@ def get_census(lib, prefix, handle, first, count):
     return out
 
 
+# avgpu_genotype (include/avida_gpu.h): one row per genotype, keys ascending
+GENOTYPE_DTYPE = np.dtype([("genotype_key", "<u8"), ("first_cell", "<i8"), ("num_units", "<i4"),
+                           ("genome_length", "<i4"), ("num_gestated", "<i4"), ("reserved", "<i4"),
+                           ("sum_merit", "<f8"), ("sum_fitness", "<f8"), ("sum_repro_rate", "<f8"),
+                           ("max_fitness", "<f8"), ("sum_gestation", "<i8"), ("sum_copied", "<i8")])
+assert GENOTYPE_DTYPE.itemsize == 80
+
+
+class GENOTYPE_TOTALS(C.Structure):
+    """avgpu_genotype_totals"""
+    _fields_ = [("num_organisms", C.c_int64), ("num_genotypes", C.c_int64),
+                ("sum_copied_size", C.c_int64), ("sum_executed_size", C.c_int64)]
+
+
+def get_genotypes(lib, handle):
+    """(table, totals) of a product world through avgpu_get_genotypes: the
+    table (GENOTYPE_DTYPE, keys ascending) sized to the world's genotypes.
+    The buffer starts at 1024 rows and keeps the largest size seen per
+    library; a table that has outgrown it costs one more grouping."""
+    totals = GENOTYPE_TOTALS()
+    cap = getattr(lib, "_genotype_cap", 1024)
+    while True:
+        out = np.empty(cap, dtype=GENOTYPE_DTYPE)
+        rc = lib.avgpu_get_genotypes(handle, out.ctypes.data_as(C.c_void_p), cap, C.byref(totals))
+        if rc >= 0:
+            return out[:rc], totals
+        if rc != -1 or totals.num_genotypes <= cap:      # not the "cap too small" refusal
+            raise RuntimeError(f"avgpu_get_genotypes: {lib.avgpu_last_error().decode()}")
+        cap = lib._genotype_cap = int(totals.num_genotypes) + int(totals.num_genotypes) // 4 + 16
+
+
 # C-ABI symbols declared in include/avida_gpu.h (checked by tests/test_capi.py)
 EXPORTED = [
     "avgpu_last_error", "avgpu_cfg_defaults", "avgpu_check_cfg", "avgpu_create", "avgpu_destroy", "avgpu_sync",
@@ -199,6 +230,7 @@ EXPORTED = [
     "avgpu_last_step_insts", "avgpu_last_kernel_ms", "avgpu_kernel_times", "avgpu_counters",
     "avgpu_state_digests", "avgpu_set_rng_mode", "avgpu_run_serial_updates", "avgpu_set_serial_streams",
     "avgpu_get_serial_state", "avgpu_set_serial_state", "avgpu_set_timing",
+    "avgpu_get_genotypes", "avgpu_last_genotypes_ms",
 ]
 
 
@@ -445,6 +477,10 @@ def load_product(path=None):
     lib.avgpu_update_totals.argtypes = [C.c_void_p, C.c_void_p]
     lib.avgpu_update_run.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AvgpuUpdateStats)]
     lib.avgpu_set_stream.argtypes = [C.c_void_p, C.c_void_p]
+    # the genotype table: the product only (the oracle has the census)
+    lib.avgpu_get_genotypes.restype = C.c_int
+    lib.avgpu_get_genotypes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GENOTYPE_TOTALS)]
+    lib.avgpu_last_genotypes_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     if path is None:
         _lib = lib
     return lib

@@ -114,6 +114,15 @@ struct avgpu_world {
   int last_k = 1;
   int tile_sub = 0, tile_k = 1, tile_sub_next = 0;
   uint32_t tile_key = 0;
+  // the genotype table (avgpu_get_genotypes): scratch allocated at the first
+  // call (in allocs), the row buffer grown to the largest table seen
+  GtScratch gt = {};
+  bool gt_ready = false;
+  avgpu_genotype* gt_rows = nullptr;
+  int64_t gt_rows_cap = 0;
+  hipEvent_t ev_gt[4] = {};
+  double gt_ms = 0.0;
+  int64_t gt_bytes = 0;
 
   template <typename T>
   int alloc(T** p, size_t count) {
@@ -710,6 +719,8 @@ int avgpu_destroy(avgpu_world* w) {
   for (void* p : w->allocs) hipFree(p);
   if (w->rec_buf) hipFree(w->rec_buf);
   for (double* p : w->srec_buf) if (p) hipFree(p);
+  if (w->gt_rows) hipFree(w->gt_rows);
+  for (hipEvent_t e : w->ev_gt) if (e) hipEventDestroy(e);
   if (w->ev0) hipEventDestroy(w->ev0);
   if (w->ev1) hipEventDestroy(w->ev1);
   for (int i = 0; i < avgpu_world::RING; i++) {
@@ -1306,6 +1317,84 @@ int avgpu_get_census(avgpu_world* w, int64_t first, int64_t count, avgpu_census*
   HIPCHK(hipMemcpyAsync(out, d, count * sizeof(avgpu_census), hipMemcpyDeviceToHost, w->stream));
   HIPCHK(hipStreamSynchronize(w->stream));
   hipFree(d);
+  return 0;
+}
+
+// the grouping's scratch: 24 B per cell for the two (key, cell) buffers of
+// the sort, the per-tile histograms and segment tiles on top (under 1 B per cell)
+static int genotypes_alloc(avgpu_world* w) {
+  if (w->gt_ready) return 0;
+  GtScratch& S = w->gt;
+  S.n = w->W.n;
+  S.nblk = (S.n + GT_SORT_TILE - 1) / GT_SORT_TILE;
+  S.ntile = (S.n + GT_SEG_TILE - 1) / GT_SEG_TILE;
+  int rc = 0;
+  for (int k = 0; k < 2 && rc == 0; k++) {
+    if ((rc = w->alloc(&S.key[k], (size_t)S.n)) < 0) break;
+    rc = w->alloc(&S.cell[k], (size_t)S.n);
+  }
+  if (rc == 0) rc = w->alloc(&S.hist, (size_t)256 * S.nblk);
+  if (rc == 0) rc = w->alloc(&S.dtot, 256);
+  if (rc == 0) rc = w->alloc(&S.tile_agg, (size_t)S.ntile);
+  if (rc == 0) rc = w->alloc(&S.carry, (size_t)S.ntile);
+  if (rc == 0) rc = w->alloc(&S.tile_flag, (size_t)S.ntile);
+  if (rc == 0) rc = w->alloc(&S.tile_tails, (size_t)S.ntile);
+  if (rc == 0) rc = w->alloc(&S.row_off, (size_t)S.ntile);
+  if (rc == 0) rc = w->alloc(&S.totals, 1);
+  if (rc < 0) return rc;
+  for (hipEvent_t& e : w->ev_gt) HIPCHK(hipEventCreate(&e));
+  w->gt_ready = true;
+  return 0;
+}
+
+int avgpu_get_genotypes(avgpu_world* w, avgpu_genotype* out, int64_t cap, avgpu_genotype_totals* totals) {
+  if (!w || cap < 0) return fail(AVGPU_EINVAL, "avgpu_get_genotypes: NULL world or negative cap");
+  if (w->W.tiled) return fail(AVGPU_EUNSUPPORTED, "genotype table on strip tiles");
+  if (w->W.n >= (1ll << 31) - GT_SORT_TILE) return fail(AVGPU_EUNSUPPORTED, "genotype table of 2^31 cells or more");
+  int rc = genotypes_alloc(w);
+  if (rc < 0) return rc;
+  const GtScratch& S = w->gt;
+  HIPCHK(hipMemsetAsync(S.totals, 0, sizeof(avgpu_genotype_totals), w->stream));
+  HIPCHK(hipEventRecord(w->ev_gt[0], w->stream));
+  launch_genotype_group(w->W, S, w->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(w->ev_gt[1], w->stream));
+  avgpu_genotype_totals t;
+  COPY_SYNC(w, &t, S.totals, sizeof(t), hipMemcpyDeviceToHost);
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, w->ev_gt[0], w->ev_gt[1]));
+  w->gt_ms = ms;
+  w->gt_bytes = sizeof(t);
+  if (totals) *totals = t;
+  if (!out || cap == 0) return 0;
+  if (cap < t.num_genotypes)
+    return fail(AVGPU_EINVAL, "avgpu_get_genotypes: cap " + std::to_string(cap) + " rows, the table has " +
+                                  std::to_string(t.num_genotypes));
+  if (t.num_genotypes == 0) return 0;
+  if (w->gt_rows_cap < t.num_genotypes) {       // the stream is idle (COPY_SYNC above)
+    if (w->gt_rows) hipFree(w->gt_rows);
+    w->gt_rows = nullptr;
+    w->gt_rows_cap = 0;
+    const int64_t want = std::min<int64_t>(S.n, std::max<int64_t>(t.num_genotypes + t.num_genotypes / 4, 1024));
+    hipError_t e = hipMalloc(&w->gt_rows, (size_t)want * sizeof(avgpu_genotype));
+    if (e != hipSuccess) return fail(AVGPU_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    w->gt_rows_cap = want;
+  }
+  HIPCHK(hipEventRecord(w->ev_gt[2], w->stream));
+  launch_genotype_rows(w->W, S, w->gt_rows, w->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(w->ev_gt[3], w->stream));
+  COPY_SYNC(w, out, w->gt_rows, (size_t)t.num_genotypes * sizeof(avgpu_genotype), hipMemcpyDeviceToHost);
+  HIPCHK(hipEventElapsedTime(&ms, w->ev_gt[2], w->ev_gt[3]));
+  w->gt_ms += ms;
+  w->gt_bytes += t.num_genotypes * (int64_t)sizeof(avgpu_genotype);
+  return (int)t.num_genotypes;
+}
+
+int avgpu_last_genotypes_ms(avgpu_world* w, double* device_ms, int64_t* bytes_copied) {
+  if (!w) return fail(AVGPU_EINVAL, "NULL world");
+  if (device_ms) *device_ms = w->gt_ms;
+  if (bytes_copied) *bytes_copied = w->gt_bytes;
   return 0;
 }
 

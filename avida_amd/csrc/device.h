@@ -825,6 +825,34 @@ void launch_set_states(const DevWorld& W, hipStream_t s, int64_t first, int64_t 
                        const uint8_t* codes, int cap);
 void launch_state_digest(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, uint64_t* d_out);
 void launch_get_census(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, avgpu_census* d_out);
+// the genotype table (genotypes.hip).  GtAgg: what a run of
+// sorted positions of one genome key adds up to; GtScratch: the world's
+// scratch for the grouping, allocated at the first avgpu_get_genotypes.
+struct GtAgg {
+  int32_t n, ng;            // members, members with a completed gestation
+  double sm, sf, sr, mx;    // merit, fitness, 1 / gestation sums; max fitness (gestated members)
+  int64_t sg, sc;           // gestation time, copied size sums (gestated members)
+  int32_t first, pad;       // lowest cell
+};
+static_assert(sizeof(GtAgg) == 64, "GtAgg");
+static_assert(sizeof(avgpu_genotype) == 80 && sizeof(avgpu_genotype_totals) == 32, "genotype table rows");
+#define GT_SORT_TILE 4096   // (key, cell) pairs per radix sort block
+#define GT_SEG_TILE 256     // sorted positions per segment tile
+struct GtScratch {
+  int64_t n, nblk, ntile;   // cells, sort tiles, segment tiles
+  uint64_t* key[2];         // [n] key - 1 (ping-pong)
+  int32_t* cell[2];         // [n]
+  uint32_t* hist;           // [256][nblk]
+  uint32_t* dtot;           // [256]
+  GtAgg* tile_agg;          // [ntile] the tile's open tail part
+  GtAgg* carry;             // [ntile] the open segment's parts before the tile
+  int32_t* tile_flag;       // [ntile] a segment starts in the tile
+  int32_t* tile_tails;      // [ntile] segments ending in the tile
+  int64_t* row_off;         // [ntile] segments ending before the tile
+  avgpu_genotype_totals* totals;
+};
+void launch_genotype_group(const DevWorld& W, const GtScratch& S, hipStream_t s);
+void launch_genotype_rows(const DevWorld& W, const GtScratch& S, avgpu_genotype* d_out, hipStream_t s);
 void launch_merit_total(const DevWorld& W, hipStream_t s, double* d_totals, double* d_scratch);
 // strip tiles
 void launch_tile_partials(const DevWorld& W, hipStream_t s, double* d_out, int reset);

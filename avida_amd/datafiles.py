@@ -138,6 +138,9 @@ class StatsRecorder:
             live = c["genotype_key"] != 0
             copied = float(c["copied_size"][live].astype("f8").sum()) / n
             executed = float(c["executed_size"][live].astype("f8").sum()) / n
+        elif n and getattr(self.arbiter, "totals", None) is not None:   # fed a genotype table
+            t = self.arbiter.totals
+            copied, executed = float(t.sum_copied_size) / n, float(t.sum_executed_size) / n
         f.row([s.update, avg(s.sum_merit), avg(s.sum_gestation), avg(s.sum_fitness), 0, 0, copied, executed, 0,
                (s.births / n) if n else 0.0, 0, 0, s.ave_generation, 0, 0, 0])
 

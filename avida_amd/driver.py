@@ -97,6 +97,11 @@ class ProductWorld:
     def census(self, first=0, count=None):
         return capi.get_census(self.lib, self.p, self.h, first, self.ncells - first if count is None else count)
 
+    def genotypes(self):
+        """(table, totals): the census grouped by key on the device
+        (avgpu_get_genotypes)"""
+        return capi.get_genotypes(self.lib, self.h)
+
     def resources(self, spatial=False):
         lv = (C.c_double * max(1, self.nres))()
         self._call("get_resources", self.h, lv, None)
@@ -164,6 +169,13 @@ class Driver:
     def _org(self, name):
         return files.read_org(os.path.join(self.config_dir, name), self.iset)
 
+    def _classify(self):
+        """the arbiter takes the world's genotype table: the device's where
+        the world has one, else the census grouped on the host"""
+        w = self.world
+        table, totals = w.genotypes() if hasattr(w, "genotypes") else systematics.table_from_census(w.census())
+        self.arbiter.update_table(table, totals, max(self.update, 0))
+
     def _action(self, action, args):
         w = self.world
         if action == "Inject":
@@ -186,7 +198,7 @@ class Driver:
             self.rec.injected += end - start
         if action in ("Inject", "InjectAll") or action.lower() == "injectsequence":
             if self.arbiter is not None:      # injected units are classified at once
-                self.arbiter.update(w.census(), max(self.update, 0))
+                self._classify()
             return
         if action == "PrintCountData":
             self.rec.print_count(*args[:1])
@@ -212,7 +224,7 @@ class Driver:
             self.rec.injected += population.load_population(
                 w, self.iset, os.path.join(self.config_dir, args[0]), w.ncells, offset)
             if self.arbiter is not None:
-                self.arbiter.update(w.census(), max(self.update, 0))
+                self._classify()
         elif action == "SaveCheckpoint":
             name = args[0] if args else f"checkpoint-{self.update}.npz"
             w.checkpoint(os.path.join(self.data_dir, name))
@@ -235,7 +247,7 @@ class Driver:
                 self.rec.begin_update()
             self.rec.end_update(self.world.run_update())
             if self.arbiter is not None:
-                self.arbiter.update(self.world.census(), self.update)
+                self._classify()
             for trig, start, action, args in self.events:
                 if _fires(trig, start, self.update):
                     self._action(action, args)

@@ -99,6 +99,8 @@ def save_population(world, iset: files.InstSet, arbiter, path, update, cap=capi.
     if arbiter is None:
         arbiter = systematics.GenotypeArbiter()
         arbiter.update(census, update)
+    elif arbiter.cell_order is None:      # classified from genotype tables: the cells by key, one argsort
+        arbiter.set_cells(census)
     handlers = iset.handlers
     inst_set = iset.name or "heads_default"
     n = len(census)

@@ -9,8 +9,12 @@ reaches THRESHOLD organisms or becomes the most abundant (nameGenotype,
 when its last organism dies (removeGenotype, :499-530).
 
 Here the device keys each birth genome once at activation (avgpu_census,
-include/avida_gpu.h) and this class groups a world's census by key after
-each update.  It is a batch restatement: births and deaths of one update are
+include/avida_gpu.h) and groups the living cells by key into a genotype table
+(avgpu_get_genotypes: one row per key with its abundance, first cell and
+sums; table_from_census is the same table in numpy, for worlds without the
+device call).  GenotypeArbiter.update_table classifies one table after each
+update; update(census) does the same from a census and also keeps every
+genotype's cells.  It is a batch restatement: births and deaths of one update are
 applied together, in cell order, because the batch world itself places and
 activates an update's offspring together.  Rules:
 
@@ -44,8 +48,11 @@ fitness is DBL_MIN (an empty cDoubleSum, as the reference's first rows show).
 from __future__ import annotations
 
 import sys
+from collections.abc import Mapping
 
 import numpy as np
+
+from . import capi
 
 GOLD = 0x9E3779B97F4A7C15
 M64 = (1 << 64) - 1
@@ -85,107 +92,290 @@ def name_letters(num: int) -> str:
     return "".join(reversed(a))
 
 
-class Genotype:
-    __slots__ = ("id", "key", "length", "update_born", "num_units", "total_units",
-                 "threshold", "name", "cells")
+def _totals(num_organisms=0, num_genotypes=0, sum_copied=0, sum_executed=0):
+    t = capi.GENOTYPE_TOTALS()
+    t.num_organisms, t.num_genotypes = int(num_organisms), int(num_genotypes)
+    t.sum_copied_size, t.sum_executed_size = int(sum_copied), int(sum_executed)
+    return t
 
-    def __init__(self, gid, key, length, update_born):
-        self.id, self.key, self.length, self.update_born = gid, key, length, update_born
-        self.num_units = 0
-        self.total_units = 0
-        self.threshold = False
-        self.name = "%03d-no_name" % length
-        self.cells = None
+
+def table_from_census(census):
+    """The genotype table of a census, (table, totals): the numpy statement of
+    avgpu_get_genotypes (include/avida_gpu.h), the same fields
+    (capi.GENOTYPE_DTYPE) in the same order -- one row per distinct non-zero
+    key, keys ascending.  The device table is tested against it, and worlds
+    without a device table (the oracle) feed the arbiter through it.
+
+    Summation: every double sum is accumulated one member at a time in
+    ascending cell order (numpy.bincount with weights).  The device adds the
+    same members in a tree, so the two agree to num_gestated * 2^-52
+    relative (all terms >= 0), not bit for bit; integers and max_fitness are
+    exact.  A census row counts as living when its key is non-zero."""
+    key = census["genotype_key"]
+    alive = np.flatnonzero(key != 0)
+    uk, first, inv, counts = np.unique(key[alive], return_index=True, return_inverse=True,
+                                       return_counts=True)
+    m = len(uk)
+    table = np.zeros(m, dtype=capi.GENOTYPE_DTYPE)
+    totals = _totals(len(alive), m, census["copied_size"][alive].sum(dtype=np.int64),
+                     census["executed_size"][alive].sum(dtype=np.int64))
+    if m == 0:
+        return table, totals
+    inv = inv.reshape(-1)
+    first_cell = alive[first]
+    table["genotype_key"] = uk
+    table["first_cell"] = first_cell
+    table["num_units"] = counts
+    table["genome_length"] = census["genome_length"][first_cell]
+    gest = census["gestation_time"][alive]
+    done = gest > 0
+    gi, rows = inv[done], census[alive[done]]
+    gt = rows["gestation_time"].astype(np.float64)
+    table["num_gestated"] = np.bincount(gi, minlength=m)
+    table["sum_merit"] = np.bincount(gi, weights=rows["merit"], minlength=m)
+    table["sum_fitness"] = np.bincount(gi, weights=rows["fitness"], minlength=m)
+    table["sum_repro_rate"] = np.bincount(gi, weights=1.0 / gt, minlength=m)
+    sg, sc = np.zeros(m, dtype=np.int64), np.zeros(m, dtype=np.int64)
+    np.add.at(sg, gi, rows["gestation_time"])
+    np.add.at(sc, gi, rows["copied_size"])
+    table["sum_gestation"], table["sum_copied"] = sg, sc
+    if len(gi):
+        o = np.lexsort((rows["fitness"], gi))            # by genotype, fitness ascending
+        gs = gi[o]
+        last = np.flatnonzero(np.r_[gs[1:] != gs[:-1], True])
+        table["max_fitness"][gs[last]] = rows["fitness"][o][last]
+    return table, totals
+
+
+def cells_by_key(census):
+    """(keys ascending, order, bounds): the living cells of key keys[j] are
+    order[bounds[j]:bounds[j + 1]], ascending -- one stable argsort"""
+    alive = np.flatnonzero(census["genotype_key"] != 0)
+    k = census["genotype_key"][alive]
+    o = np.argsort(k, kind="stable")
+    ks = k[o]
+    heads = np.flatnonzero(np.r_[True, ks[1:] != ks[:-1]]) if len(ks) else np.zeros(0, dtype=np.int64)
+    return ks[heads], alive[o], np.r_[heads, len(ks)]
+
+
+class Genotype:
+    """One active genotype, read through the arbiter's arrays.  The object
+    for a key stays the same while the genotype lives; after its removal it
+    keeps its last values with num_units 0."""
+    __slots__ = ("_a", "id", "key", "length", "update_born", "_gone")
+
+    def __init__(self, arbiter, key, j):
+        self._a, self.key = arbiter, key
+        self.id, self.length = int(arbiter.ids[j]), int(arbiter.lengths[j])
+        self.update_born = int(arbiter.born[j])
+        self._gone = None
+
+    def _j(self):
+        return self._a._index(self.key)
+
+    def _retire(self):
+        """called before the arbiter drops the genotype"""
+        self._gone = (self.total_units, self.threshold, self.name)
+
+    @property
+    def num_units(self):
+        return 0 if self._gone else int(self._a.units[self._j()])
+
+    @property
+    def total_units(self):
+        return self._gone[0] if self._gone else int(self._a.total[self._j()])
+
+    @property
+    def threshold(self):
+        return self._gone[1] if self._gone else bool(self._a.thr[self._j()])
+
+    @property
+    def name(self):
+        if self._gone:
+            return self._gone[2]
+        k = int(self._a.name_no[self._j()])
+        return "%03d-%s" % (self.length, name_letters(k - 1)) if k else "%03d-no_name" % self.length
+
+    @property
+    def cells(self):
+        a = self._a
+        if self._gone or a.cell_order is None:
+            return None
+        j = self._j()
+        return a.cell_order[a.cell_bounds[j]:a.cell_bounds[j + 1]]
+
+
+class _Active(Mapping):
+    """key -> Genotype over the arbiter's sorted key array"""
+
+    def __init__(self, arbiter):
+        self._a = arbiter
+
+    def __len__(self):
+        return len(self._a.keys)
+
+    def __iter__(self):
+        return (int(k) for k in self._a.keys)
+
+    def __contains__(self, key):
+        return self._a._index(key) >= 0
+
+    def __getitem__(self, key):
+        a = self._a
+        j = a._index(key)
+        if j < 0:
+            raise KeyError(key)
+        g = a._views.get(int(key))
+        if g is None:
+            g = a._views[int(key)] = Genotype(a, int(key), j)
+        return g
 
 
 class GenotypeArbiter:
-    """Batch restatement of Systematics::GenotypeArbiter over census rows."""
+    """Batch restatement of Systematics::GenotypeArbiter over genotype
+    tables.  The active genotypes are parallel arrays in ascending key order
+    (the table's order): matching a table against them, abundances, totals and
+    the dominant are array operations; Python runs per genotype only for
+    those that cross the threshold (names) and for Genotype objects a caller
+    asked for."""
 
     def __init__(self, threshold=3):
         self.threshold = threshold
-        self.active = {}          # key -> Genotype
+        self.keys = np.zeros(0, dtype=np.uint64)
+        self.ids = np.zeros(0, dtype=np.int64)
+        self.lengths = np.zeros(0, dtype=np.int32)
+        self.born = np.zeros(0, dtype=np.int64)
+        self.units = np.zeros(0, dtype=np.int64)
+        self.total = np.zeros(0, dtype=np.int64)
+        self.thr = np.zeros(0, dtype=bool)
+        self.name_no = np.zeros(0, dtype=np.int64)   # 1 + the name's number within its size, 0 = unnamed
+        self.active = _Active(self)
+        self._views = {}
         self.next_id = 1
         self.sz_count = {}        # genome size -> names handed out
         self.tot_genotypes = 0
         self.tot_threshold = 0
-        self.best = None
-        self.census = None
+        self.best_key = None
+        self.table = None         # the last table: row j describes keys[j]
+        self.totals = None
+        self.census = None        # set by update(census) only
+        self.cell_order = self.cell_bounds = None
+
+    def _index(self, key):
+        j = int(np.searchsorted(self.keys, np.uint64(key)))
+        return j if j < len(self.keys) and int(self.keys[j]) == int(key) else -1
 
     def _name(self, size):
+        """the next name number of a genome size, plus 1"""
         k = self.sz_count.get(size, 0)
         self.sz_count[size] = k + 1
-        return "%03d-%s" % (size, name_letters(k))
+        return k + 1
+
+    def update_table(self, table, totals, update):
+        """Classify one genotype table (capi.GENOTYPE_DTYPE rows, keys
+        ascending; table_from_census or capi.get_genotypes)."""
+        tk = table["genotype_key"]
+        m, old = len(tk), len(self.keys)
+        pos = np.searchsorted(self.keys, tk)
+        found = np.zeros(m, dtype=bool)
+        if old:
+            found = self.keys[np.minimum(pos, old - 1)] == tk
+        dst = np.flatnonzero(found)
+        src = pos[dst]
+        fresh = np.flatnonzero(~found)
+        if self._views and len(src) < old:            # genotypes that disappear
+            gone = np.ones(old, dtype=bool)
+            gone[src] = False
+            for k in self.keys[gone]:
+                g = self._views.pop(int(k), None)
+                if g is not None:
+                    g._retire()
+        units = table["num_units"].astype(np.int64)
+
+        def carry(a, fill):
+            out = np.full(m, fill, dtype=a.dtype)
+            out[dst] = a[src]
+            return out
+        ids, lengths, born = carry(self.ids, 0), carry(self.lengths, 0), carry(self.born, update)
+        prev, total = carry(self.units, 0), carry(self.total, 0)
+        thr, name_no = carry(self.thr, False), carry(self.name_no, 0)
+        # new ids in order of the first cell holding the key
+        by_cell = fresh[np.argsort(table["first_cell"][fresh], kind="stable")]
+        ids[by_cell] = self.next_id + np.arange(len(fresh))
+        lengths[fresh] = table["genome_length"][fresh]
+        self.next_id += len(fresh)
+        self.tot_genotypes += len(fresh)
+        total += np.maximum(0, units - prev)
+        self.keys, self.ids, self.lengths, self.born = tk.copy(), ids, lengths, born
+        self.units, self.total, self.thr, self.name_no = units, total, thr, name_no
+        self.table, self.totals = table, totals
+        self.census = self.cell_order = self.cell_bounds = None
+        if m == 0:
+            self.best_key = None
+            return
+        top = units.max()
+        bj = self._index(self.best_key) if self.best_key is not None else -1
+        if bj < 0 or units[bj] != top:
+            cand = np.flatnonzero(units == top)
+            bj = int(cand[np.argmin(ids[cand])])
+            self.best_key = int(tk[bj])
+        cross = ~thr & (units >= self.threshold)
+        cross[bj] = not thr[bj]
+        cj = np.flatnonzero(cross)
+        for j in cj[np.argsort(ids[cj])]:              # names in id order
+            thr[j] = True
+            name_no[j] = self._name(int(lengths[j]))
+            self.tot_threshold += 1
 
     def update(self, census, update):
-        """Classify one census (capi.CENSUS_DTYPE rows, one per cell)."""
+        """Classify one census (capi.CENSUS_DTYPE rows, one per cell); the
+        genotypes then know their cells."""
+        table, totals = table_from_census(census)
+        self.update_table(table, totals, update)
         self.census = census
-        alive = np.nonzero(census["genotype_key"] != 0)[0]
-        keys = census["genotype_key"][alive]
-        uk, first, inv, counts = np.unique(keys, return_index=True, return_inverse=True,
-                                           return_counts=True)
-        order = np.argsort(inv, kind="stable")
-        bounds = np.concatenate([[0], np.cumsum(counts)])
-        present = {}
-        for j in np.argsort(first, kind="stable"):          # first-cell order
-            k = int(uk[j])
-            g = self.active.get(k)
-            if g is None:
-                c0 = alive[first[j]]
-                g = Genotype(self.next_id, k, int(census["genome_length"][c0]), update)
-                self.next_id += 1
-                self.tot_genotypes += 1
-                self.active[k] = g
-            prev = g.num_units
-            g.num_units = int(counts[j])
-            g.total_units += max(0, g.num_units - prev)
-            g.cells = alive[order[bounds[j]:bounds[j + 1]]]
-            present[k] = g
-        for k in [k for k in self.active if k not in present]:
-            g = self.active.pop(k)
-            g.num_units = 0
-            if self.best is g:
-                self.best = None
-        if not present:
-            self.best = None
-            return
-        top = max(g.num_units for g in present.values())
-        if self.best is None or self.best.num_units != top:
-            self.best = min((g for g in present.values() if g.num_units == top), key=lambda g: g.id)
-        for g in sorted(present.values(), key=lambda g: g.id):
-            if not g.threshold and (g.num_units >= self.threshold or g is self.best):
-                g.threshold = True
-                g.name = self._name(g.length)
-                self.tot_threshold += 1
+        self.set_cells(census)
+
+    def set_cells(self, census):
+        """give the genotypes of the last table their cell lists from a
+        census of the same world state"""
+        keys, self.cell_order, self.cell_bounds = cells_by_key(census)
+        if not np.array_equal(keys, self.keys):
+            raise ValueError("the census does not hold the genotypes of the last table")
 
     # ---- cStats / data-file views ----
     def num_genotypes(self):
-        return len(self.active)
+        return len(self.keys)
 
     def num_threshold(self):
-        return sum(1 for g in self.active.values() if g.threshold)
+        return int(self.thr.sum())
 
     def dominant(self):
-        return self.best
+        return self.active[self.best_key] if self.best_key is not None else None
+
+    @property
+    def best(self):
+        return self.dominant()
 
     def genotype_averages(self, g):
         """(merit, gestation, fitness, repro rate, copied size, max fitness)
-        over g's organisms with a completed gestation"""
-        rows = self.census[g.cells]
-        rows = rows[rows["gestation_time"] > 0]
-        if len(rows) == 0:
+        over g's organisms with a completed gestation: the table's sums over
+        num_gestated"""
+        r = self.table[self._index(g.key)]
+        n = int(r["num_gestated"])
+        if n == 0:
             return 0.0, 0.0, 0.0, 0.0, 0.0, DBL_MIN
-        gest = rows["gestation_time"].astype(np.float64)
-        return (float(rows["merit"].mean()), float(gest.mean()), float(rows["fitness"].mean()),
-                float((1.0 / gest).mean()), float(rows["copied_size"].astype(np.float64).mean()),
-                float(rows["fitness"].max()))
+        return (float(r["sum_merit"]) / n, int(r["sum_gestation"]) / n, float(r["sum_fitness"]) / n,
+                float(r["sum_repro_rate"]) / n, int(r["sum_copied"]) / n, float(r["max_fitness"]))
 
     def dominant_row(self, update):
         """One PrintDominantData row (actions/PrintActions.cc:5405-5440), or
         None with no organisms (the reference writes nothing then)."""
-        g = self.best
+        g = self.dominant()
         if g is None:
             return None
         merit, gest, fit, repro, copied, maxfit = self.genotype_averages(g)
         # births / breed true / depth / breed in need lineage records: 0
         return [update, merit, gest, fit, repro, g.length, copied, 0.0, g.num_units,
                 0, 0, 0, 0, maxfit, g.id, g.name]
+
+

@@ -550,6 +550,40 @@ typedef struct avgpu_census {
   int32_t num_divides;
 } avgpu_census;
 
+/* ---- genotype table ----
+ * The census grouped by key on the device: one row per distinct non-zero
+ * genotype_key among the living cells, rows ascending by key.  It replaces
+ * the bookkeeping GenotypeArbiter::ClassifyNewUnit / AdjustGenotype keep per
+ * genotype (systematics/GenotypeArbiter.cc:280-468: which genotypes exist,
+ * their abundances) and the sums Genotype::HandleUnitGestation accumulates
+ * (systematics/Genotype.cc:289-301), so the host classifies from a table of
+ * genotypes instead of 48 B per cell.  The per-cell values are
+ * avgpu_census's.  The table is a function of the world alone: the double
+ * sums are taken in a fixed order (cells ascending within a key, a fixed
+ * reduction shape), never with floating-point atomics; two calls on an
+ * unchanged world return identical bytes. */
+typedef struct avgpu_genotype {
+  uint64_t genotype_key;
+  int64_t first_cell;      /* lowest cell id holding the key */
+  int32_t num_units;       /* living cells with the key */
+  int32_t genome_length;   /* genome_length of first_cell */
+  int32_t num_gestated;    /* members with gestation_time > 0 */
+  int32_t reserved;        /* 0 */
+  double sum_merit;        /* the five sums and the max run over the */
+  double sum_fitness;      /* gestated members only:                 */
+  double sum_repro_rate;   /* sum of 1.0 / gestation_time            */
+  double max_fitness;      /* 0 when num_gestated == 0               */
+  int64_t sum_gestation;
+  int64_t sum_copied;
+} avgpu_genotype;
+
+typedef struct avgpu_genotype_totals {
+  int64_t num_organisms;       /* living cells */
+  int64_t num_genotypes;       /* rows of the full table */
+  int64_t sum_copied_size;     /* over all living cells: average.dat's */
+  int64_t sum_executed_size;   /* copied / executed size columns       */
+} avgpu_genotype_totals;
+
 /* ---- random streams ------------------------------
  * Apto::RNG::AvidaRNG (main/cWorld.h:72) is absent, so every draw of the path
  * is a uniform u in [0,1) with the reference's interface on top (P(p) = u < p,
@@ -581,6 +615,20 @@ int avgpu_get_states(avgpu_world* w, int64_t first_cell, int64_t count,
  * cell): the data PrintDominantData / PrintCountData's genotype columns and
  * the dominant genotype's averages are computed from on the host. */
 int avgpu_get_census(avgpu_world* w, int64_t first_cell, int64_t count, avgpu_census* out);
+/* The genotype table into host memory, in stream order behind the queued
+ * updates and complete on return; only the rows that exist are copied.
+ * Returns the number of rows written.  totals (may be NULL) is filled by
+ * every grouping.  out == NULL or cap == 0 only counts: totals is filled, 0
+ * is returned.  0 < cap < totals->num_genotypes: AVGPU_EINVAL naming the
+ * count needed, totals filled, out untouched.  A strip tile:
+ * AVGPU_EUNSUPPORTED.  The world is never changed; the scratch (24 B per cell
+ * and 80 B per row) is allocated by the first call and kept. */
+int avgpu_get_genotypes(avgpu_world* w, avgpu_genotype* out, int64_t cap,
+                        avgpu_genotype_totals* totals);
+/* Timing of the last avgpu_get_genotypes (no reference equivalent): the
+ * device time of its kernels in ms (HIP events on the world's stream) and
+ * the bytes it copied to the host. */
+int avgpu_last_genotypes_ms(avgpu_world* w, double* device_ms, int64_t* bytes_copied);
 /* Verification (no reference equivalent): one 64-bit digest per cell of
  * cells first .. first+count-1 into host memory -- a chained mix over the 32-bit
  * words of the cell's state record, as avgpu_get_states returns it, and its
