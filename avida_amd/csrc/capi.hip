@@ -53,9 +53,6 @@ struct avgpu_world {
   int device = 0;
   hipStream_t stream = nullptr;      // current stream (own or external)
   hipStream_t own_stream = nullptr;
-  hipStream_t aux_stream[3] = {};   // [0] class 1, [1] classes 2 + 3 beside class 0 (world updates); [2] unused
-  hipEvent_t ev_fork = nullptr, ev_join[3] = {};
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // event ring around interpreter phases (avgpu_last_kernel_ms,
   // avgpu_kernel_times): ev[i][0] before class 0, ev[i][k+1] after class k
   static const int RING = 512;
@@ -293,19 +290,16 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   W.seed_lo = (uint32_t)c.seed;
   W.seed_hi = (uint32_t)(c.seed >> 32);
   // interpreter slow-op batching (interp.hip); AVGPU_SLOW_BATCH overrides (tuning)
-  W.slow_batch = 12;
-  if (const char* e = getenv("AVGPU_SLOW_BATCH")) W.slow_batch = std::max(1, std::min(64, atoi(e)));
+  W.slow_batch = env_int("AVGPU_SLOW_BATCH", 12, 1, 64);
   // the newborn pass's own: 1 -- its duration is its longest newborn's, and a
   // parked lane waiting for a batch lengthens exactly that path (1.344 ->
   // 1.323 ms per update, profiles/r06g_ab_nbsb.txt)
-  W.nb_slow_batch = 1;
-  if (const char* e = getenv("AVGPU_NB_SLOW_BATCH")) W.nb_slow_batch = std::max(1, std::min(64, atoi(e)));
+  W.nb_slow_batch = env_int("AVGPU_NB_SLOW_BATCH", 1, 1, 64);
   // the kernels that queue their IO task checks (interp.hip IOQ): IO, ~45 % of
   // the bench population's parks, parks only on a full queue there, so the
   // same wait fills half a batch (12 against 6 against 8 against 4:
   // profiles/ioq_ab.txt)
-  W.ioq_slow_batch = 6;
-  if (const char* e = getenv("AVGPU_IOQ_SLOW_BATCH")) W.ioq_slow_batch = std::max(1, std::min(64, atoi(e)));
+  W.ioq_slow_batch = env_int("AVGPU_IOQ_SLOW_BATCH", 6, 1, 64);
   W.row0 = 0;
   W.global_rows = c.world_y;
   W.rows = c.world_y;
@@ -403,20 +397,7 @@ avgpu_world* create_world(const avgpu_cfg* cfg, int device, int64_t n, bool test
   w->device = device;
   if (n <= 0) n = (int64_t)cfg->world_x * cfg->world_y;
   if (n <= 0 || n > (1ll << 30)) { delete w; fail(AVGPU_EINVAL, "bad cell count"); return nullptr; }
-  // The list classes' aux streams get the higher priority: their blocks
-  // become ready together with class 0's (both wait for k_allot_sort) and must
-  // take their CUs first -- a class-3 block needs a whole CU's LDS, which a
-  // CU full of class-0 blocks frees only when all of them have retired.
-  int prio_lo = 0, prio_hi = 0;
-  if (hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi) != hipSuccess) prio_lo = prio_hi = 0;
   if (hipStreamCreateWithFlags(&w->own_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipStreamCreateWithPriority(&w->aux_stream[0], hipStreamNonBlocking, prio_hi) != hipSuccess ||
-      hipStreamCreateWithPriority(&w->aux_stream[1], hipStreamNonBlocking, prio_hi) != hipSuccess ||
-      hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&w->ev_join[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&w->ev_join[1], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&w->ev_join[2], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreate(&w->ev0) != hipSuccess || hipEventCreate(&w->ev1) != hipSuccess ||
       hipHostMalloc((void**)&w->h_pred, 4 * sizeof(long long), hipHostMallocMapped | hipHostMallocCoherent) !=
           hipSuccess ||
       hipHostMalloc((void**)&w->h_stage, 2 * sizeof(DevWorld), hipHostMallocDefault) != hipSuccess ||
@@ -473,6 +454,15 @@ int ready(avgpu_world* w) {
   if (!w) return fail(AVGPU_EINVAL, "NULL world");
   if (!w->instset_loaded) return fail(AVGPU_ESTATE, "avgpu_load_instset not called");
   if (!w->env_loaded) return fail(AVGPU_ESTATE, "avgpu_load_env not called");
+  return 0;
+}
+
+// ready for a batch update (avgpu_run_update, avgpu_update_run)
+int batch_ready(avgpu_world* w) {
+  const int rc = ready(w);
+  if (rc < 0) return rc;
+  if (w->cfg.birth_method == 5)
+    return fail(AVGPU_EUNSUPPORTED, "BIRTH_METHOD 5 (the reaper queue) runs on the serial world only");
   return 0;
 }
 
@@ -606,13 +596,13 @@ int drain_ring(avgpu_world* w, int keep) {
 }
 
 // point d_W at a device copy of the world descriptor equal to the host copy,
-// uploading it into the other slot when neither holds it.  The upload is
-// stream-ordered after every launch queued before it (the only readers of
-// that slot: the aux streams of AVGPU_NO_MIX join the stream within their
-// update, avgpu_set_stream synchronises), from pinned staging whose last
-// upload is waited for -- no stream synchronisation on the update path
-// (it cost ~30 us of idle GPU per configs[4] update, whose resource buffers
-// swap every update).
+// uploading it into the other slot when neither holds it.  Only launches on
+// the world's own stream read a slot, and the upload is queued on that stream
+// behind them, so stream order alone makes it safe (avgpu_set_stream
+// synchronises before the stream changes).  It comes from pinned staging
+// whose last upload is waited for -- no stream synchronisation on the update
+// path (it cost ~30 us of idle GPU per configs[4] update, whose resource
+// buffers swap every update).
 int push_world(avgpu_world* w) {
   for (int k = 0; k < 2; k++)
     if (w->validv[k] && memcmp(&w->pushedv[k], &w->W, sizeof(DevWorld)) == 0) {
@@ -644,8 +634,7 @@ int interpret(avgpu_world* w, int mode, int64_t first, int64_t count, bool sorte
   const int i = w->ring_head;
   if (timed) HIPCHK(hipEventRecord(w->ring[i][0], w->stream));
   launch_interpret_classes(w->W, w->d_W, mode, w->stream, first, count, &launches,
-                           timed ? &w->ring[i][1] : nullptr, sorted,
-                           sorted ? w->aux_stream : nullptr, w->ev_fork, w->ev_join);
+                           timed ? &w->ring[i][1] : nullptr, sorted);
   HIPCHK(hipGetLastError());
   if (timed) {
     w->ring_head = (i + 1) % avgpu_world::RING;
@@ -654,8 +643,6 @@ int interpret(avgpu_world* w, int mode, int64_t first, int64_t count, bool sorte
   w->last_launches = launches;
   return 0;
 }
-
-int update_run(avgpu_world* w, const double* dev_totals, avgpu_update_stats* out);
 
 // An update's batch steps (oracle choose_k): avgpu_cfg.sub_updates
 // when set; else the more of two rules over the last step's predictor: with E
@@ -721,18 +708,11 @@ int avgpu_destroy(avgpu_world* w) {
   for (double* p : w->srec_buf) if (p) hipFree(p);
   if (w->gt_rows) hipFree(w->gt_rows);
   for (hipEvent_t e : w->ev_gt) if (e) hipEventDestroy(e);
-  if (w->ev0) hipEventDestroy(w->ev0);
-  if (w->ev1) hipEventDestroy(w->ev1);
   for (int i = 0; i < avgpu_world::RING; i++) {
     for (int k = 0; k <= NUM_CLASSES; k++)
       if (w->ring[i][k]) hipEventDestroy(w->ring[i][k]);
   }
   if (w->own_stream) hipStreamDestroy(w->own_stream);
-  for (int k = 0; k < 3; k++) {
-    if (w->aux_stream[k]) { hipStreamSynchronize(w->aux_stream[k]); hipStreamDestroy(w->aux_stream[k]); }
-    if (w->ev_join[k]) hipEventDestroy(w->ev_join[k]);
-  }
-  if (w->ev_fork) hipEventDestroy(w->ev_fork);
   if (w->h_pred) hipHostFree(w->h_pred);
   if (w->h_stage) hipHostFree(w->h_stage);
   for (int k = 0; k < 2; k++)
@@ -965,12 +945,47 @@ int avgpu_step(avgpu_world* w, int64_t first, int64_t count, const int32_t* budg
   return rc;
 }
 
-// after launch_world_pre: the spatial step wrote res_amount_alt; later
-// launches read the new amounts
+// after an update's first launch_world_begin / launch_tile_pre: the spatial
+// step wrote res_amount_alt; later launches read the new amounts
 static void after_resources_begin(avgpu_world* w) {
   DevWorld& W = w->W;
   if (res_stepped(W)) std::swap(W.res_amount, W.res_amount_alt);
   W.res_first = 0;
+}
+
+// the scheduler's key of batch step `sub` of the current update's K
+static uint32_t step_key(const avgpu_world* w, int sub, int K) {
+  return (uint32_t)w->update * (uint32_t)K + (uint32_t)sub;
+}
+
+// One update of a single world in K batch steps, each: total
+// merit, allotment, class lists and the class-0 order; interpretation;
+// placement; the newborn pass.  own_totals: the picks come from the world's
+// own totals, and the last step's placement publishes the predictor; else
+// from the totals handed in in d_totals[0..1] (K = 1).
+static int run_steps(avgpu_world* w, int K, bool own_totals, avgpu_update_stats* out) {
+  for (int sub = 0; sub < K; sub++) {
+    const uint32_t key = step_key(w, sub, K);
+    launch_world_begin(w->W, w->stream, w->d_totals, w->d_totals + 8, key, sub, K, own_totals);
+    if (sub == 0) after_resources_begin(w);
+    HIPCHK(hipGetLastError());
+    const int rc = interpret(w, AVGPU_MODE_WORLD, 0, w->W.n, true);
+    if (rc < 0) return rc;
+    const bool last = sub == K - 1, pred = last && own_totals;
+    if (pred) w->pred_seq++;
+    launch_world_post(w->W, w->stream, key, sub, K, pred ? w->d_pred : nullptr, w->pred_seq);
+    launch_newborns(w->W, w->d_W, w->stream);
+    // statistics only when asked for: a run without them (out == NULL) leaves
+    // the reduction to avgpu_get_stats / avgpu_stats_vector, or skips it
+    launch_world_end(w->W, w->stream, w->d_stats, out != nullptr && last);
+    HIPCHK(hipGetLastError());
+  }
+  w->pred_pending = own_totals;
+  w->last_k = K;
+  w->stats_stale = out == nullptr;
+  w->update++;
+  if (out) return avgpu_get_stats(w, out);
+  return 0;
 }
 
 int avgpu_update_totals(avgpu_world* w, double* dev_totals) {
@@ -983,10 +998,8 @@ int avgpu_update_totals(avgpu_world* w, double* dev_totals) {
 }
 
 int avgpu_update_run(avgpu_world* w, const double* dev_totals, avgpu_update_stats* out) {
-  int rc = ready(w);
+  const int rc = batch_ready(w);
   if (rc < 0) return rc;
-  if (w->cfg.birth_method == 5)
-    return fail(AVGPU_EUNSUPPORTED, "BIRTH_METHOD 5 (the reaper queue) runs on the serial world only");
   if (!dev_totals) return fail(AVGPU_EINVAL, "dev_totals is NULL");
   if (w->cfg.sub_updates > 1)
     return fail(AVGPU_EUNSUPPORTED, "sub_updates > 1 needs the world's own totals (no handed-in totals)");
@@ -996,39 +1009,20 @@ int avgpu_update_run(avgpu_world* w, const double* dev_totals, avgpu_update_stat
   if (dev_totals != w->d_totals)
     HIPCHK(hipMemcpyAsync(w->d_totals, dev_totals, 2 * sizeof(double), hipMemcpyDeviceToDevice, w->stream));
   w->pred_pending = false;
-  launch_world_pre(w->W, w->stream, w->d_totals, w->d_totals + 8, w->ev_fork, (uint32_t)w->update);
-  after_resources_begin(w);
-  HIPCHK(hipGetLastError());
-  rc = interpret(w, AVGPU_MODE_WORLD, 0, w->W.n, true);
-  if (rc < 0) return rc;
-  launch_world_post(w->W, w->stream, (uint32_t)w->update, 0, 1);
-  launch_newborns(w->W, w->d_W, w->stream);
-  // statistics only when asked for: a run without them (out == NULL) leaves
-  // the reduction to avgpu_get_stats / avgpu_stats_vector, or skips it
-  launch_world_end(w->W, w->stream, w->d_stats, out != nullptr);
-  HIPCHK(hipGetLastError());
-  w->last_k = 1;
-  w->stats_stale = out == nullptr;
-  w->update++;
-  if (out) return avgpu_get_stats(w, out);
-  return 0;
+  return run_steps(w, 1, false, out);
 }
 
 int avgpu_run_update(avgpu_world* w, avgpu_update_stats* out) {
-  int rc = ready(w);
+  const int rc = batch_ready(w);
   if (rc < 0) return rc;
-  if (w->cfg.birth_method == 5)
-    return fail(AVGPU_EUNSUPPORTED, "BIRTH_METHOD 5 (the reaper queue) runs on the serial world only");
   if (w->use_global) {                 // totals handed in (avgpu_update_totals / tiles)
     w->use_global = false;
     return avgpu_update_run(w, w->d_totals, out);
   }
-  // K batch steps (choose_k: avgpu_cfg.sub_updates, or the
-  // last update's predictor), each: total merit, allotment, class lists and
-  // the class-0 order; interpretation; placement; the newborn pass.  The
-  // predictor comes back by mapped memory from the last step's placement:
-  // the host waits for it (here, at the next update) while the GPU runs the
-  // rest of that update.
+  // K batch steps (run_steps; choose_k: avgpu_cfg.sub_updates, or the last
+  // update's predictor).  The predictor comes back by mapped memory from the
+  // last step's placement: the host waits for it (here, at the next update)
+  // while the GPU runs the rest of that update.
   if (w->pred_pending) {
     // the last step's placement launch published the predictor into
     // coherent mapped memory, then its sequence number (k_place_claim0): the
@@ -1048,28 +1042,7 @@ int avgpu_run_update(avgpu_world* w, avgpu_update_stats* out) {
     w->pred_pending = false;
   }
   const int K = choose_k(w->cfg, w->pred_acc, w->pred_n, false, w->pred_cnt);
-  for (int sub = 0; sub < K; sub++) {
-    const uint32_t key = (uint32_t)w->update * (uint32_t)K + (uint32_t)sub;
-    launch_world_begin(w->W, w->stream, w->d_totals, w->d_totals + 8, w->ev_fork, key, sub, K);
-    if (sub == 0) after_resources_begin(w);
-    HIPCHK(hipGetLastError());
-    rc = interpret(w, AVGPU_MODE_WORLD, 0, w->W.n, true);
-    if (rc < 0) return rc;
-    const bool last = sub == K - 1;
-    if (last) w->pred_seq++;
-    launch_world_post(w->W, w->stream, key, sub, K, last ? w->d_pred : nullptr, w->pred_seq);
-    launch_newborns(w->W, w->d_W, w->stream);
-    // statistics only when asked for: a run without them (out == NULL) leaves
-    // the reduction to avgpu_get_stats / avgpu_stats_vector, or skips it
-    launch_world_end(w->W, w->stream, w->d_stats, out != nullptr && last);
-    HIPCHK(hipGetLastError());
-  }
-  w->pred_pending = true;
-  w->last_k = K;
-  w->stats_stale = out == nullptr;
-  w->update++;
-  if (out) return avgpu_get_stats(w, out);
-  return 0;
+  return run_steps(w, K, true, out);
 }
 
 // the serial world's state, allocated on first use: merit sum tree,
@@ -1998,8 +1971,8 @@ int avgpu_tile_begin_step(avgpu_world* w, const double* dev_gathered, int ntiles
     }
   }
   // (the counters were cleared by avgpu_tile_partials' launch at step 0)
-  const uint32_t key = (uint32_t)w->update * (uint32_t)K + (uint32_t)sub;
-  launch_tile_pre(w->W, w->stream, dev_gathered, ntiles, w->d_totals, w->ev_fork, key, sub, K);
+  const uint32_t key = step_key(w, sub, K);
+  launch_tile_pre(w->W, w->stream, dev_gathered, ntiles, w->d_totals, key, sub, K);
   if (sub == 0) after_resources_begin(w);
   HIPCHK(hipGetLastError());
   rc = interpret(w, AVGPU_MODE_WORLD, 0, w->W.n, true);

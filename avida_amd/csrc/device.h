@@ -12,6 +12,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/avida_gpu.h"
 
@@ -116,9 +117,9 @@ struct DevWorld {
   int32_t* budget;    // [n]  instructions left in this update
   // [n] size class k_allot / k_classify_uniform gave the cell's slice this
   // update (0..3, ACLASS_NONE: no slice).  Only those kernels write it: the
-  // class-0 launch and k_window_sort select their cells by this tag, never by
-  // the live mem_size / budget that list classes running beside them on the
-  // aux streams rewrite (a list-class slice that divides down to a class-0
+  // class-0 launch and k_window_order select their cells by this tag, never by
+  // the live mem_size / budget that the list classes running in the same
+  // launch rewrite (a list-class slice that divides down to a class-0
   // size must not be picked up by class 0 in the same update).
   uint8_t* aclass;
   uint8_t* tape;      // [n][TAPE_SLOT]
@@ -753,47 +754,47 @@ __device__ __forceinline__ int need_of(int m, uint32_t ctl, double size_range) {
 
 // ---------------------------------------------------------------------------
 // host-side launchers (defined next to their kernels)
-struct LaunchInfo {
-  hipStream_t stream;
-  hipEvent_t ev0, ev1;
-  bool timed;
-};
+// a tuning knob of the environment: its integer value when set and within
+// [lo, hi], else dflt (callers cache it per call site)
+static inline int env_int(const char* name, int dflt, int lo, int hi) {
+  const char* e = getenv(name);
+  const int v = e ? atoi(e) : dflt;
+  return (v >= lo && v <= hi) ? v : dflt;
+}
 
 // class 0 runs densely over cells [first, first+count); classes 1..3 over their lists
 // after_class[k] (optional): event recorded after the class-k launch
 // dW: device copy of W (avgpu_world::push_world)
-// aux (optional): three streams on which the classes 1..3 of k_allot's
-// lists run concurrently with class 0 (ev_fork / ev_join[3] order them)
+// sorted: a world update's main pass (class 0 follows k_window_order's windows)
 void launch_serial_update(const DevWorld& W, const DevWorld* dW, hipStream_t s);
 void launch_serial_post(const DevWorld& W, hipStream_t s, double* stats);
 void launch_reset_counts(const DevWorld& W, hipStream_t s);
 void launch_interpret_classes(const DevWorld& W, const DevWorld* dW, int mode, hipStream_t s,
                               int64_t first, int64_t count, int* launches,
-                              hipEvent_t* after_class = nullptr, bool sorted = false,
-                              hipStream_t* aux = nullptr, hipEvent_t ev_fork = nullptr,
-                              hipEvent_t* ev_join = nullptr);
+                              hipEvent_t* after_class = nullptr, bool sorted = false);
 // class-0 windows: k_allot's budgets sorted (descending) inside windows of
 // SORT_WIN cells, so that a wave's 64 organisms get similar time slices
 #define SORT_WIN 32768
-// k_allot_sort's buckets: budgets 0 .. SORT_BUCKETS-3 (larger ones share the
+// k_window_order's buckets: budgets 0 .. SORT_BUCKETS-3 (larger ones share the
 // last of them), then one bucket for the window's cells that are not class 0
 #define SORT_BUCKETS 258
 bool class_timing_all();   // AVGPU_CLASS_TIMING (interp.hip)
-bool mix_lists();          // list classes inside class 0's launch (interp.hip; AVGPU_NO_MIX=1 off)
 void launch_age_tick(const DevWorld& W, hipStream_t s);
 // sub-update `sub` of `nsub` (avgpu_cfg.sub_updates): the
 // resources step and the update's counters are reset at sub 0 only; the key
 // of the scheduler's node draws is update x nsub + sub (the caller's `update`)
-void launch_world_begin(const DevWorld& W, hipStream_t s, double* d_totals, double* d_scratch,
-                        hipEvent_t lists_ready, uint32_t update, int sub = 0, int nsub = 1);
+// own_totals: the picks come from this world's own totals (k_block_counts
+// mode 0); else from the totals handed in in d_totals[0..1] (avgpu_update_totals
+// + an all-reduce of every world's {total weight, organisms}), this world's
+// share by cMultiProcessWorld's formula (mode 2)
+void launch_world_begin(const DevWorld& W, hipStream_t s, double* d_totals, double* d_scratch, uint32_t update,
+                        int sub, int nsub, bool own_totals);
 // a sub-update's share of the update's picks n (oracle sub_share)
 __host__ __device__ __forceinline__ long long sub_share(long long n, int s, int K) {
   return K == 1 ? n : (n * (s + 1)) / K - (n * s) / K;
 }
-void launch_world_pre(const DevWorld& W, hipStream_t s, double* d_totals, double* d_scratch, hipEvent_t lists_ready,
-                      uint32_t update, bool reset = true);
 void launch_tile_pre(const DevWorld& W, hipStream_t s, const double* d_gathered, int ntiles, double* d_totals,
-                     hipEvent_t lists_ready, uint32_t update, int sub = 0, int nsub = 1);
+                     uint32_t update, int sub = 0, int nsub = 1);
 // allotment draw of organism (lo, hi) in update u (oracle allot_draw)
 __device__ __forceinline__ uint32_t allot_draw(uint32_t lo, uint32_t hi, uint32_t update) {
   return lowbias32(lowbias32(update * 0x85EBCA6BU + hi) ^ lo ^ 0x27D4EB2FU);

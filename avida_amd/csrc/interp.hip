@@ -2022,7 +2022,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     const bool alive = !(fl & F_DEAD);
     const bool spill = (fl & F_SPILL) != 0;
     if (!alive) ctl &= ~CTL_ALIVE;
-    // a death frees the cell for this update's placement (k_allot_total
+    // a death frees the cell for this update's placement (k_allot
     // marked the living cells occupied)
     if (mode == AVGPU_MODE_WORLD && alive0 && !alive) W.occ[cell] = 0;
     W.ctl[cell] = (ctl & ~CTL_FRESH) | (sdie ? CTL_SPECDIE : 0u);
@@ -2179,8 +2179,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
 // The mixed class-0 launch (nmix > 0, world updates): its first nmix blocks
 // run the list classes 1 / 2 / 3 in class-0 blocks (MIX_B1 / MIX_B2 / MIX_B3
 // blocks, each a grid-stride over its list in chunks of 64 / kslot
-// organisms), the rest are class 0 -- one launch, so the list classes need no
-// aux stream, no fork / join events and no head start on class 0.
+// organisms), the rest are class 0 -- one launch on the world's one stream.
 #define MIX_B1 512
 #define MIX_B2 16
 #define MIX_B3 8
@@ -2575,12 +2574,7 @@ __global__ __launch_bounds__(64, 1) void k_serial_update(const DevWorld* __restr
 
 // lanes per wave of the spill rows (AVGPU_SPILL_LPW overrides for sweeps)
 static int spill_lpw() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AVGPU_SPILL_LPW");
-    const int x = e ? atoi(e) : 0;
-    v = (x >= 1 && x <= 64) ? x : 1;
-  }
+  static const int v = env_int("AVGPU_SPILL_LPW", 1, 1, 64);
   return v;
 }
 
@@ -2589,26 +2583,12 @@ static int spill_lpw() {
 // of queue time, and the three spill-row launches sit on the update's
 // critical path
 bool class_timing_all() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AVGPU_CLASS_TIMING");
-    v = (e && atoi(e) == 1) ? 1 : 0;
-  }
+  static const int v = env_int("AVGPU_CLASS_TIMING", 0, 0, 1);
   return v == 1;
 }
 
 // the knobs the DEF instantiation fixes, at the reference's defaults
 // (avgpu_cfg_defaults; main/cAvidaConfig.h)
-// AVGPU_NO_MIX=1: the list classes on their own aux-stream launches (A/B)
-bool mix_lists() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("AVGPU_NO_MIX");
-    v = (e && atoi(e) == 1) ? 0 : 1;
-  }
-  return v == 1;
-}
-
 static bool def_knobs(const DevWorld& W) {
   return W.alloc_method != 2 && W.require_allocate == 1 && W.max_label_exe == 1 && W.cfg_min_genome == 0 &&
          W.cfg_max_genome == 0 && W.merit_default_bonus == 0.0 && W.inherit_merit == 1 &&
@@ -2616,6 +2596,44 @@ static bool def_knobs(const DevWorld& W) {
          W.th_par_del == 0 && W.size_range == 2.0 && W.min_exe_lines == 0.5 &&
          W.min_copied_lines == 0.5 && W.required_bonus == 0.0 && W.default_bonus == 1.0 && W.rand_total <= 256 &&
          !W.copy_ext && !W.track_age && W.no_mut_mask == 0 && !W.div_req;
+}
+
+// The k_interpret instantiation of a launch, chosen once per launch_classes
+// call for its class-0 launch and its rows alike.
+// IP_DEF: a world update (main pass or newborn pass) at the simple environment
+// and default knobs runs the specialised interpreter (SIMPLE, DEF) in its list
+// classes and spill rows as in class 0 -- the spill rows run alone after
+// class 0, latency-bound on their longest slice, so every instruction of the
+// generic paths is on the update's critical path
+// (DEF defers the divide's phenotype work to placement round 0: only world
+// updates run placement -- avgpu_step(MODE_WORLD) takes the general path)
+// IP_DEF_RES: the same with finite resources behind the simple reactions, configs[4]
+// IP_SIMPLE: class 0 of any other world-mode launch at the simple environment
+// without resources (the rows have no such kernel: they run the generic one)
+enum Interp { IP_GENERIC, IP_SIMPLE, IP_DEF, IP_DEF_RES };
+static Interp interp_of(const DevWorld& W, int mode, bool update) {
+  if (mode != AVGPU_MODE_WORLD) return IP_GENERIC;
+  const bool res = W.env_res_mask != 0u;
+  if (update && W.env_simple && def_knobs(W)) return res ? IP_DEF_RES : IP_DEF;
+  return (W.env_simple && !res) ? IP_SIMPLE : IP_GENERIC;
+}
+// C0W: class 0 of a world-mode launch; outside world mode class 0 has the
+// generic kernel only
+template <int S, bool REC, bool C0W, bool NB>
+static void launch_interpret(Interp v, unsigned grid, hipStream_t s, const DevWorld* dW, int cls, int row, int mode,
+                             int64_t first, int64_t count, int srt, int lpw, int nmix = 0) {
+#define LAUNCH(SIMPLE, DEF, RES) \
+  hipLaunchKernelGGL((k_interpret<S, REC, C0W, SIMPLE, DEF, RES, NB>), dim3(grid), dim3(64), 0, s, dW, cls, row, \
+                     mode, first, count, srt, lpw, nmix)
+  if constexpr (C0W || S != CLASS0_SIZE) {
+    if (v == IP_DEF_RES) { LAUNCH(true, true, true); return; }
+    if (v == IP_DEF) { LAUNCH(true, true, false); return; }
+  }
+  if constexpr (C0W) {
+    if (v == IP_SIMPLE) { LAUNCH(true, false, false); return; }
+  }
+  LAUNCH(false, false, false);
+#undef LAUNCH
 }
 
 // NB: the newborn pass of a world update (launch_newborns): the same launches
@@ -2626,145 +2644,75 @@ static bool def_knobs(const DevWorld& W) {
 #define NB_BLOCKS 2048
 template <bool REC, bool NB>
 static void launch_classes(const DevWorld& W, const DevWorld* dW, int mode, hipStream_t s,
-                           int64_t first, int64_t count, int* launches, hipEvent_t* after_class,
-                           bool sorted, hipStream_t* aux, hipEvent_t ev_fork, hipEvent_t* ev_join) {
-  const int pfl = (!NB && sorted && mode == AVGPU_MODE_WORLD) ? 2 : 0;
+                           int64_t first, int64_t count, int* launches, hipEvent_t* after_class, bool sorted) {
+  const bool c0w = mode == AVGPU_MODE_WORLD;
+  const int pfl = (!NB && sorted && c0w) ? 2 : 0;
   const int srt = ((!NB && sorted && first == 0 && count == W.n) ? 1 : 0) | pfl;
   const bool tall = class_timing_all();
   const unsigned blocks = NB ? (unsigned)NB_BLOCKS : (unsigned)((count + 63) / 64);
-  // list classes: a capped grid strides over the list (length known on the
-  // device only).  The caps follow the blocks a CU holds (LDS: 3 of class 1,
-  // 1 of classes 2 / 3) and the lists' usual lengths (class 1 ~1 %, classes
-  // 2 / 3 and the spill rows tens of organisms): a 2048-block grid of
-  // 132-KiB class-3 blocks costs 8 dispatch rounds even when its list is
-  // empty.
-  const unsigned lb = std::min(blocks, 768u);
-  const unsigned lb_small = std::min(blocks, 256u);
-  // classes 2 / 3 beside class 0: a handful of blocks.  Each of their blocks
-  // needs most of a CU's LDS (99 / 132 KiB), so a 256-block grid queued behind
-  // the running class-0 blocks for most of class 0's duration (rocprof: 0.52
-  // ms average k_interpret<2048> with lists of tens of organisms) and took
-  // CUs away from it as their blocks dispatched one by one.
-  const unsigned lb_c2 = std::min(blocks, 8u), lb_c3 = std::min(blocks, 4u);
   if (blocks == 0) {
     if (after_class)
       for (int k = 0; k < 4; k++) hipEventRecord(after_class[k], s);
     return;
   }
-  // Organisms k_allot put in classes 1..3 (list rows 1..3) do not depend on
-  // class 0; with an aux stream they run beside it and fill the CUs its tail
-  // leaves idle.  Spills (rows 4..6) run after both, in class order.
-  // list classes and spill rows of a world update at the simple environment
-  // and default knobs: the same specialised interpreter as class 0's (SIMPLE,
-  // DEF) -- the spill rows run alone after class 0, latency-bound on their
-  // longest slice, so every instruction of the generic paths is on the
-  // update's critical path
-  // (DEF defers the divide's phenotype work to placement round 0: only world
-  // updates run placement -- avgpu_step(MODE_WORLD) takes the general path)
-  // (RES: the same with finite resources behind the simple reactions, configs[4])
-  const bool fast = (NB || sorted) && mode == AVGPU_MODE_WORLD && W.env_simple && def_knobs(W);
-  const bool res = W.env_res_mask != 0u;
-  auto row = [&](int S, dim3 grid, hipStream_t st, int cls, int r, int lpw) {
-#define ROW_LAUNCH(SZ) \
-    do { if (fast && res) hipLaunchKernelGGL((k_interpret<SZ, REC, false, true, true, true, NB>), grid, dim3(64), 0, st, dW, cls, r, mode, first, count, pfl, lpw); \
-         else if (fast) hipLaunchKernelGGL((k_interpret<SZ, REC, false, true, true, false, NB>), grid, dim3(64), 0, st, dW, cls, r, mode, first, count, pfl, lpw); \
-         else hipLaunchKernelGGL((k_interpret<SZ, REC, false, false, false, false, NB>), grid, dim3(64), 0, st, dW, cls, r, mode, first, count, pfl, lpw); } while (0)
-    if (S == CLASS1_SIZE) ROW_LAUNCH(CLASS1_SIZE);
-    else if (S == CLASS2_SIZE) ROW_LAUNCH(CLASS2_SIZE);
-    else ROW_LAUNCH(CLASS3_SIZE);
-#undef ROW_LAUNCH
-  };
-  auto list = [&](int k, hipStream_t st) {
-    if (k == 1) row(CLASS1_SIZE, dim3(lb), st, 1, 1, 64);
-    if (k == 2) row(CLASS2_SIZE, dim3(lb_c2), st, 2, 2, 64);
-    if (k == 3) row(CLASS3_SIZE, dim3(lb_c3), st, 3, 3, 64);
-    // classes 2 + 3 in one launch of class 3's slots: both start at the fork,
-    // before class 0's blocks fill the CUs (a class-3 block launched behind
-    // class 2 waited ~0.5 ms for a CU with all of its LDS free)
-    if (k == 23) row(CLASS3_SIZE, dim3(lb_c2 + lb_c3), st, -1, 2, 64);
-  };
-  // Two aux streams (class 1; classes 2 + 3, which are short): with the
-  // world's stream that is three HIP streams, so they keep distinct hardware
-  // queues (GPU_MAX_HW_QUEUES = 4); a third aux stream shared a queue with
-  // the world's stream and serialised class 3 in front of class 0.  The aux
-  // lists start after k_allot, beside the window sort, so that they take their
-  // CUs before class 0 and end well inside it (forked after the sort they only
-  // got CUs as class-0 waves retired and ended ~40-55 us after class 0).
-  // the list classes inside class 0's launch (MIX_BLOCKS leading blocks):
-  // sorted world updates, unless AVGPU_NO_MIX=1 (A/B)
-  const bool mix = NB || (aux && mix_lists());
+  // the list classes inside class 0's launch (MIX_BLOCKS leading blocks): the
+  // newborn pass, or a sorted world update
+  const bool mix = NB || (sorted && c0w);
   const int nmix = mix ? MIX_BLOCKS : 0;
-  const unsigned cblocks = blocks + (unsigned)nmix;
-  if (!NB && aux && !mix) {
-    // ev_fork: recorded by launch_world_pre right after k_allot built the lists
-    for (int k = 0; k < 2; k++) hipStreamWaitEvent(aux[k], ev_fork, 0);
-    list(1, aux[0]);
-    list(2, aux[1]);
-    list(3, aux[1]);
-    // one join for the world's stream: aux 0 takes in aux 1 (classes 2 + 3,
-    // short) off the critical path; each wait queued on the world's stream
-    // costs ~10 us of dead time there even when its event has long completed
-    hipEventRecord(ev_join[1], aux[1]);
-    hipStreamWaitEvent(aux[0], ev_join[1], 0);
-    hipEventRecord(ev_join[0], aux[0]);
-  }
-  if (fast && res)
-    hipLaunchKernelGGL((k_interpret<CLASS0_SIZE, REC, true, true, true, true, NB>), dim3(cblocks), dim3(64), 0, s, dW, 0, 0, mode, first, count, srt, 64, nmix);
-  else if (fast)
-    hipLaunchKernelGGL((k_interpret<CLASS0_SIZE, REC, true, true, true, false, NB>), dim3(cblocks), dim3(64), 0, s, dW, 0, 0, mode, first, count, srt, 64, nmix);
-  else if (mode == AVGPU_MODE_WORLD && W.env_simple && W.env_res_mask == 0u)
-    hipLaunchKernelGGL((k_interpret<CLASS0_SIZE, REC, true, true, false, false, NB>), dim3(cblocks), dim3(64), 0, s, dW, 0, 0, mode, first, count, srt, 64, nmix);
-  else if (mode == AVGPU_MODE_WORLD)
-    hipLaunchKernelGGL((k_interpret<CLASS0_SIZE, REC, true, false, false, false, NB>), dim3(cblocks), dim3(64), 0, s, dW, 0, 0, mode, first, count, srt, 64, nmix);
-  else if (!NB)
-    hipLaunchKernelGGL((k_interpret<CLASS0_SIZE, REC>), dim3(blocks), dim3(64), 0, s, dW, 0, 0, mode, first, count, srt, 64);
+  const Interp v = interp_of(W, mode, mix);
+#define ROW(SZ, grid, cls, r, lpw) \
+  launch_interpret<SZ, REC, false, NB>(v, grid, s, dW, cls, r, mode, first, count, pfl, lpw)
+  if (c0w)
+    launch_interpret<CLASS0_SIZE, REC, true, NB>(v, blocks + (unsigned)nmix, s, dW, 0, 0, mode, first, count, srt, 64,
+                                                 nmix);
+  else if constexpr (!NB)
+    launch_interpret<CLASS0_SIZE, REC, false, false>(v, blocks, s, dW, 0, 0, mode, first, count, srt, 64);
   if (after_class) hipEventRecord(after_class[0], s);
   // Spill rows run after class 0, alone on the chip and latency-bound on their
   // longest remaining slice; spread over waves (spill_lpw lanes each), a
   // wave's iterations no longer pay for its other lanes' divergent paths.
-  // Row 4 holds only class-0 organisms (those that outgrew its slots), so it
-  // starts right behind class 0, and the joins with the aux streams (their
-  // lists ended inside class 0) are queued while it runs instead of in front
-  // of it (~17 us per update of event waits on the critical path).
   const int slpw = spill_lpw();
-  // row 4 (class 0's spills): a world launch's class-0 waves continue their
-  // own spills (k_interpret, C0W), other launches run the row
-  const bool c0w = mode == AVGPU_MODE_WORLD;
-  if (mix) {
-    // no join: the lists ran in class 0's launch
-  } else if (aux) {
-    if (!c0w) row(CLASS1_SIZE, dim3(lb_small), s, 1, 4, slpw);
-    hipStreamWaitEvent(s, ev_join[0], 0);
-  } else {
-    for (int k = 1; k <= 3; k++) list(k, s);
-    if (!c0w) row(CLASS1_SIZE, dim3(lb_small), s, 1, 4, slpw);
+  const unsigned lb_small = std::min(blocks, 256u);
+  if (!mix) {
+    // avgpu_step: the list classes follow class 0 on the stream.  A capped
+    // grid strides over each list (length known on the device only).  The
+    // caps follow the blocks a CU holds (LDS: 3 of class 1, 1 of classes
+    // 2 / 3) and the lists' usual lengths (class 1 ~1 %, classes 2 / 3 and the
+    // spill rows tens of organisms): a 2048-block grid of 132-KiB class-3
+    // blocks costs 8 dispatch rounds even when its list is empty.
+    ROW(CLASS1_SIZE, std::min(blocks, 768u), 1, 1, 64);
+    ROW(CLASS2_SIZE, std::min(blocks, 8u), 2, 2, 64);
+    ROW(CLASS3_SIZE, std::min(blocks, 4u), 3, 3, 64);
+    // row 4 (class 0's spills): a world launch's class-0 waves continue their
+    // own spills (k_interpret, C0W), other launches run the row
+    if (!c0w) ROW(CLASS1_SIZE, lb_small, 1, 4, slpw);
   }
   if (after_class && tall) hipEventRecord(after_class[1], s);
   // spill rows 5 + 6 (beyond classes 1 / 2) in one launch of class 3's slots
-  // (all three spill rows in one class-3 launch after the join measured 8 us
-  // slower per update than these two launches: row 4's organisms ran slower
-  // in class 3's slots than the saved launch gap)
-  row(CLASS3_SIZE, dim3(std::min(lb_small, 64u)), s, -1, 5, slpw);
+  // (all three spill rows in one class-3 launch measured 8 us slower per
+  // update than these two launches: row 4's organisms ran slower in class 3's
+  // slots than the saved launch gap)
+  ROW(CLASS3_SIZE, std::min(lb_small, 64u), -1, 5, slpw);
+#undef ROW
   if (after_class && tall) { hipEventRecord(after_class[2], s); hipEventRecord(after_class[3], s); }
   if (launches) *launches += 5;
 }
 
 // RECORDED streams launch the REC instantiations (device.h DevWorld::rec)
 void launch_interpret_classes(const DevWorld& W, const DevWorld* dW, int mode, hipStream_t s,
-                              int64_t first, int64_t count, int* launches, hipEvent_t* after_class,
-                              bool sorted, hipStream_t* aux, hipEvent_t ev_fork, hipEvent_t* ev_join) {
+                              int64_t first, int64_t count, int* launches, hipEvent_t* after_class, bool sorted) {
   if (W.rec)
-    launch_classes<true, false>(W, dW, mode, s, first, count, launches, after_class, sorted, aux, ev_fork, ev_join);
+    launch_classes<true, false>(W, dW, mode, s, first, count, launches, after_class, sorted);
   else
-    launch_classes<false, false>(W, dW, mode, s, first, count, launches, after_class, sorted, aux, ev_fork, ev_join);
+    launch_classes<false, false>(W, dW, mode, s, first, count, launches, after_class, sorted);
 }
 
 // the newborn pass of a world update's batch step (after k_activate)
 void launch_newborns(const DevWorld& W, const DevWorld* dW, hipStream_t s) {
   if (W.rec)
-    launch_classes<true, true>(W, dW, AVGPU_MODE_WORLD, s, 0, W.n, nullptr, nullptr, false, nullptr, nullptr, nullptr);
+    launch_classes<true, true>(W, dW, AVGPU_MODE_WORLD, s, 0, W.n, nullptr, nullptr, false);
   else
-    launch_classes<false, true>(W, dW, AVGPU_MODE_WORLD, s, 0, W.n, nullptr, nullptr, false, nullptr, nullptr, nullptr);
+    launch_classes<false, true>(W, dW, AVGPU_MODE_WORLD, s, 0, W.n, nullptr, nullptr, false);
 }
 
 // one serial-world update (launch_world_post's statistics follow it)

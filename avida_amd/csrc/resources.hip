@@ -422,11 +422,7 @@ static inline unsigned rblk(int64_t n) { return (unsigned)((n + 255) / 256); }
 static void launch_res_step(const DevWorld& W, hipStream_t s, const ResIds& ids, int nres, bool fused) {
   bool grav = false;
   for (int i = 0; i < nres; i++) grav |= W.res_grav_host[ids.r[i]] != 0;
-  static const int band = [] {
-    const char* e = getenv("AVGPU_RES_ROWS");
-    const int v = e ? atoi(e) : RES_ROWS;
-    return v >= 1 ? v : RES_ROWS;
-  }();
+  static const int band = env_int("AVGPU_RES_ROWS", RES_ROWS, 1, INT32_MAX);
   const int ngroups = (W.world_x + RES_COLS - 1) / RES_COLS;
   const int nwaves = ngroups * ((W.rows + band - 1) / band);
   const dim3 grid((unsigned)((nwaves + 3) / 4), (unsigned)nres);

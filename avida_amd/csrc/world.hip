@@ -1980,58 +1980,38 @@ __global__ __launch_bounds__(256) void k_reset_counts(DevWorld W) { reset_counts
 
 // the allotment of a world whose block counts are in W.blk_count: budgets,
 // class lists, occupancy; then the class-0 order
-static void launch_allot(const DevWorld& W, hipStream_t s, const double* totals, hipEvent_t lists_ready,
-                         uint32_t update, int tick = 1) {
+static void launch_allot(const DevWorld& W, hipStream_t s, const double* totals, uint32_t update, int tick) {
   // (16 blocks per workgroup: the class lists take one global atomic per
   // class and 4096 cells -- with 1024-cell workgroups those atomics on three
   // addresses serialised to ~50 us per update, profiles/r04c_tail_per_update.txt)
   hipLaunchKernelGGL(k_allot, dim3(nblk(W.n, 4096)), dim3(1024), 0, s, W, totals, update, tick);
-  // the class lists are complete: the aux streams of the list classes start
-  // here, beside the window sort, so that their blocks take CUs before class 0
-  // (with the sort folded into the allotment they start together with class 0
-  // and end ~35 us after it: profiles/r02q_tail_per_update.txt).  With the
-  // lists inside class 0's launch (mix_lists) there is no fork: an event
-  // record here left ~14 us of dead time on the world's stream
-  if (!mix_lists()) hipEventRecord(lists_ready, s);
   hipLaunchKernelGGL(k_window_order, dim3(nblk(W.n, 4096)), dim3(1024), 0, s, W);
 }
 
 // single world: block partials (k_merit_partial also zeroes the update's
-// counters), the scheduler's top tree, the allotment, the class-0 order
-void launch_world_begin(const DevWorld& W, hipStream_t s, double* totals, double* scratch,
-                        hipEvent_t lists_ready, uint32_t update, int sub, int nsub) {
+// counters), the scheduler's top tree, the allotment, the class-0 order.
+// The picks come from the world's own totals (k_block_counts mode 0) or from
+// totals handed in in totals[0..1] (mode 2; device.h)
+void launch_world_begin(const DevWorld& W, hipStream_t s, double* totals, double* scratch, uint32_t update,
+                        int sub, int nsub, bool own_totals) {
   const int64_t nb = (W.n + 255) / 256;
   int32_t* alive_partial = reinterpret_cast<int32_t*>(scratch + nb);
   if (sub == 0) launch_resources_begin(W, s);   // ProcessPreUpdate + the update's first DoUpdates
   hipLaunchKernelGGL(k_merit_partial, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, W, scratch, alive_partial,
                      (double*)nullptr, sub == 0 ? 1 : 2);
-  launch_block_counts(W, s, scratch, alive_partial, nb, 1, tree_levels(nb), totals, update, 0, sub, nsub);
-  launch_allot(W, s, totals, lists_ready, update, sub == 0 ? 1 : 0);
-}
-
-// a world whose totals were handed in (avgpu_update_totals + an all-reduce of
-// every world's {total weight, organisms}, in totals[0..1]): its block
-// partials, then this world's picks by cMultiProcessWorld's formula
-// (k_block_counts mode 2).  reset: clear the update's counters here.
-void launch_world_pre(const DevWorld& W, hipStream_t s, double* totals, double* scratch, hipEvent_t lists_ready,
-                      uint32_t update, bool reset) {
-  const int64_t nb = (W.n + 255) / 256;
-  int32_t* alive_partial = reinterpret_cast<int32_t*>(scratch + nb);
-  launch_resources_begin(W, s);   // ProcessPreUpdate + the update's first DoUpdates
-  hipLaunchKernelGGL(k_merit_partial, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, W, scratch, alive_partial,
-                     (double*)nullptr, reset ? 1 : 0);
-  launch_block_counts(W, s, scratch, alive_partial, nb, 1, tree_levels(nb), totals, update, 2);
-  launch_allot(W, s, totals, lists_ready, update);
+  launch_block_counts(W, s, scratch, alive_partial, nb, 1, tree_levels(nb), totals, update, own_totals ? 0 : 2, sub,
+                      nsub);
+  launch_allot(W, s, totals, update, sub == 0 ? 1 : 0);
 }
 
 // a strip tile: the top tree over every strip's gathered partials (mode 1),
 // then the allotment (its partials' launch cleared the counters)
 void launch_tile_pre(const DevWorld& W, hipStream_t s, const double* gathered, int ntiles, double* totals,
-                     hipEvent_t lists_ready, uint32_t update, int sub, int nsub) {
+                     uint32_t update, int sub, int nsub) {
   const int64_t nb = (W.n + 255) / 256;
   if (sub == 0) launch_resources_begin(W, s);
   launch_block_counts(W, s, gathered, nullptr, nb, ntiles, tree_levels(nb * ntiles), totals, update, 1, sub, nsub);
-  launch_allot(W, s, totals, lists_ready, update, sub == 0 ? 1 : 0);
+  launch_allot(W, s, totals, update, sub == 0 ? 1 : 0);
 }
 
 void launch_stats(const DevWorld& W, hipStream_t s, double* stats) {
@@ -2046,11 +2026,7 @@ static unsigned lane_grid(const DevWorld& W) { return (unsigned)std::min<int64_t
 // placement kernels stride over the queue; 8 blocks of 256 per CU cover it
 // (AVGPU_PLACE_GRID overrides the cap for sweeps)
 static unsigned place_grid(const DevWorld& W) {
-  static int cap = -1;
-  if (cap < 0) {
-    const char* e = getenv("AVGPU_PLACE_GRID");
-    cap = e ? std::max(1, atoi(e)) : 2048;
-  }
+  static const int cap = env_int("AVGPU_PLACE_GRID", 2048, 1, INT32_MAX);
   return (unsigned)std::min<int64_t>(nblk(W.rcap, 256), cap);
 }
 
@@ -2083,7 +2059,7 @@ void launch_reset_counts(const DevWorld& W, hipStream_t s) {
 // last round's are zeroed by k_activate): no clearing launch per round.
 void launch_world_post(const DevWorld& W, hipStream_t s, uint32_t key, int sub, int nsub, long long* pred_out,
                        long long pred_seq) {
-  // the occupancy was initialised by k_allot_total; the divide mutations
+  // the occupancy was initialised by k_allot; the divide mutations
   // ride in round 0's pick launch
   // round 0's pick (with the divide mutations beside it), then three launches
   // of resolve(m-1) + pick(m), then activation with round 3's resolve: 5

@@ -123,6 +123,98 @@ def test_world_updates_bit_exact(golden):
     assert gpu.counters(cumulative=1)[capi.CNT_BAD_RECORD] == 0
 
 
+# cells of test_handed_in_totals_equal_oracle overwritten with random genomes,
+# and their lengths: an organism that has not allocated needs a slot for three
+# times its size (device.h need_of at OFFSPRING_SIZE_RANGE 2), so 200 / 400 /
+# 1700 sites start in list classes 1 / 2 / 3 and stay there after h-alloc
+HANDED_IN_LONG = ((700, 200, 41), (1800, 400, 42), (2900, 1700, 43))
+
+
+def handed_in_world(golden):
+    """The world of test_handed_in_totals_equal_oracle: (iset, env, cfg,
+    genomes, merits) -- detail-50000.pop's 3599 organisms and the ancestor on
+    the default 60x60 torus with the merits the file records (injected without
+    them the first offspring hold 10^7 times their neighbours' merit, and the
+    world has 35 births in 25 updates), three cells overwritten with long
+    random genomes at the population's highest merit, so that every update
+    gives them a slice."""
+    iset, env, cfg = pu.load_env(golden, "instset-classic.cfg", seed=101)
+    genomes = pu.pop_genomes(golden, iset)
+    merits = [g.merit for g in files.read_pop(os.path.join(golden, "detail-50000.pop")) for _ in range(g.num_cpus)]
+    heads = files.read_instset(os.path.join(golden, "instset-heads.cfg"))
+    anc = files.read_org(os.path.join(golden, "default-heads.org"), heads)
+    genomes = genomes[:3599] + [bytes(iset.op_of_name(heads.names[o]) for o in anc)]
+    merits = merits[:3599] + [0.0]
+    assert len(genomes) == len(merits) == cfg.world_x * cfg.world_y == 3600
+    for cell, length, seed in HANDED_IN_LONG:
+        genomes[cell], = pu.random_genomes(iset, 1, length, length, seed=seed)
+        merits[cell] = max(merits)
+    return iset, env, cfg, genomes, merits
+
+
+def handed_in_view(orc, n):
+    """the oracle's state records as a numpy array, and each cell's size class
+    (device.h need_of / class_of at the default OFFSPRING_SIZE_RANGE 2)"""
+    import numpy as np
+    st = (capi.AvgpuCpuState * n)()
+    orc._call("get_states", orc.h, 0, n, st, None, None, 0)
+    s = np.frombuffer(st, dtype=np.dtype(capi.AvgpuCpuState)).copy()
+    m = s["mem_size"].astype(np.int64)
+    need = np.where(s["mal_active"] != 0, m, m + np.minimum(2 * m, CAP - m))
+    return s, np.searchsorted([320, 768, 1536], need, side="left")
+
+
+def handed_in_ran(s, cls, s2):
+    """the size classes of the organisms of s that ran a slice before s2: alive
+    in both, the same organism (its RNG key), time_used advanced"""
+    same = (s["alive"] != 0) & (s2["alive"] != 0) & (s["rng_key_lo"] == s2["rng_key_lo"]) & \
+        (s["rng_key_hi"] == s2["rng_key_hi"])
+    return set(cls[same & (s2["time_used"] > s["time_used"])].tolist())
+
+
+def test_handed_in_totals_equal_oracle(golden):
+    """Updates whose totals are handed in (avgpu_set_global_totals: the path of
+    avgpu_update_run, k_block_counts mode 2) against the oracle's: a full
+    60x60 world of evolved organisms plus three long random genomes, so that
+    the list classes 1..3 run inside class 0's launch; before each of 25
+    updates both backends get the totals of two such worlds -- twice the
+    oracle world's organisms and summed merit, not this world's own, which
+    mode 0 would also reproduce.  Every update's counters equal, then every
+    cell, field and digest; at least 100 births and a slice run in each list
+    class (the oracle alone: 4907 births, classes 0..3)."""
+    iset, env, cfg, genomes, merits = handed_in_world(golden)
+    n = len(genomes)
+    orc = ol.Backend("oracle", cfg, iset, env, ncells=n)
+    gpu = ol.Backend("gpu", cfg, iset, env, ncells=n)
+    for b in (orc, gpu):
+        b.set_orgs(0, genomes, merits, deterministic=False)
+    births, classes = 0, set()
+    s, cls = handed_in_view(orc, n)
+    for upd in range(25):
+        alive = s["alive"] != 0
+        merit, orgs = 2.0 * float(s["merit"][alive].sum()), 2 * int(alive.sum())
+        for b in (orc, gpu):
+            b._call("set_global_totals", b.h, merit, orgs)
+        so = orc.run_update()
+        sg = gpu.run_update()
+        for f in ("num_organisms", "insts_executed", "births", "deaths", "divides", "births_dropped",
+                  "births_overwritten", "births_cancelled", "cum_insts_executed", "cum_births"):
+            assert getattr(so, f) == getattr(sg, f), (upd, f, getattr(so, f), getattr(sg, f))
+        assert list(so.task_orgs) == list(sg.task_orgs), upd
+        births += so.births
+        s2, cls2 = handed_in_view(orc, n)
+        classes |= handed_in_ran(s, cls, s2)
+        s, cls = s2, cls2
+    a, oa, fa = orc.states(0, n, CAP)
+    b, ob, fb = gpu.states(0, n, CAP)
+    bad = pu.diff_states(a, b, oa, ob, fa, fb, CAP)
+    assert not bad, f"{len(bad)} mismatches: {bad[:5]}"
+    nbad, cells = pu.compare_digests(orc.digests(0, n), gpu.digests(0, n))
+    assert nbad == 0, f"{nbad} cell digests differ, first {cells}"
+    assert births >= 100 and classes >= {1, 2, 3}, (births, classes)
+    assert gpu.counters(cumulative=1)[capi.CNT_BAD_RECORD] == 0
+
+
 def test_lazy_statistics_equal_eager(golden):
     """An update run with out == NULL skips the statistics reduction (the bench
     regime); the counts still reach the running sums (folded in by the next

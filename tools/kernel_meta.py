@@ -40,14 +40,20 @@ def kernels(path):
             f.write(co)
             f.flush()
             notes = subprocess.run([READELF, "--notes", f.name], capture_output=True, text=True).stdout
+        # a kernel's entry lists its keys in alphabetical order: it opens with
+        # "- .agpr_count", and its LDS size comes before its name
         cur = {}
         for line in notes.splitlines():
-            m = re.match(r"\s+\.(\w+):\s+(.*)", line)
+            m = re.match(r"\s+(- )?\.(\w+):\s+(.*)", line)
             if not m:
                 continue
-            k, v = m.group(1), m.group(2).strip()
-            if k == "name" and "_ZN" in v or (k == "name" and v.startswith("_Z")):
-                cur = {"name": v}
+            k, v = m.group(2), m.group(3).strip()
+            if m.group(1):
+                if k != "agpr_count":
+                    continue          # an item of the entry's argument list
+                cur = {}
+            if k == "name" and v.startswith("_Z"):
+                cur["name"] = v
                 out.append(cur)
             elif k in ("vgpr_count", "agpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count",
                        "private_segment_fixed_size", "group_segment_fixed_size"):
