@@ -17,7 +17,8 @@ STACK_SIZE = 10
 MAX_LABEL = 10
 
 MODE_WORLD, MODE_TEST, MODE_FROZEN = 0, 1, 2
-# enum avgpu_counter
+# enum avgpu_counter (tests/test_capi.py holds the two lists together)
+CNT_CB0, CNT_CASE0 = 32, 38
 (CNT_INSTS, CNT_DEATHS, CNT_DIVIDES, CNT_BIRTHS, CNT_DROPPED, CNT_SPILLS, CNT_SLICES,
  CNT_LANESTEPS, CNT_C0_SLICES, CNT_C0_SITES, CNT_CLK_STAGE, CNT_CLK_LOOP, CNT_CLK_WB,
  CNT_ITERS, CNT_IT_FAST, CNT_IT_COPY, CNT_IT_SLOW, CNT_WAVES, CNT_HALO_SENT,

@@ -86,8 +86,8 @@ struct avgpu_world {
   std::vector<avgpu_cell_resource> cell_spec;
   bool env_loaded = false;
   // device scratch
-  double* d_totals = nullptr;   // [8 + partials]
-  double* d_stats = nullptr;    // [32 + partials]
+  double* d_totals = nullptr;   // [totals_words(nb)] the step totals, then k_merit_partial's scratch (device.h TOT_*)
+  double* d_stats = nullptr;    // [stats_words(nb)] the statistics vector, then k_stats_partial's rows (device.h ST_*)
   bool stats_stale = false;     // the last update ran without statistics (out == NULL)
   bool use_global = false;
   int64_t update = 0;
@@ -150,12 +150,12 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   A(merit, n); A(fitness, n); A(credit, n); A(gest_time, n); A(num_div, n);
   A(generation, n); A(copied, n); A(child_copied, n); A(executed, n);
   HIPCHK(hipMemsetAsync(W.aclass, ACLASS_NONE, n, w->stream));   // no slice allotted yet
-  A(class_list, NUM_LISTS * n); A(order, n); A(sub_hist, (size_t)((n + 4095) / 4096) * SORT_BUCKETS); A(class_count, 8); A(counters, CNT_WORDS);
+  A(class_list, NUM_LISTS * n); A(order, n); A(sub_hist, (size_t)((n + 4095) / 4096) * SORT_BUCKETS); A(class_count, CLASS_COUNT_WORDS); A(counters, CNT_WORDS);
   // birth records: one primary record per cell + overflow for further
   // offspring of one slice (device.h); test worlds never enqueue births
   W.rcap = n + (test_buffers ? 16 : std::max<int64_t>(4096, n / 4));
   const int64_t R = W.rcap;
-  A(b_count, 3); A(b_list, n); A(b_parent, R); A(b_seq, R); A(b_len, R); A(b_len0, R); A(b_edit, 5 * R);
+  A(b_count, BQ_WORDS); A(b_list, n); A(b_parent, R); A(b_seq, R); A(b_len, R); A(b_len0, R); A(b_edit, 5 * R);
   // DIV_MUT_PROB arena: three times the largest expected substitutions per
   // record plus 16 (offsets are int32); a fill past it is counted
   // (AVGPU_CNT_SUB_OVERFLOW), never written
@@ -200,7 +200,7 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   // occupancy, owners and the four placement rounds' claims, each with the two
   // ghost rows a strip tile keeps after its n cells
   const int64_t ng = n + 2 * (int64_t)c.world_x;
-  A(occ, ng); A(claim, ng); A(claim2, ng); A(owner, ng); A(killt, n); A(sdone, n); A(ran, n); A(sched, 12); A(pacc, NSHARD * PACC_STRIDE);
+  A(occ, ng); A(claim, ng); A(claim2, ng); A(owner, ng); A(killt, n); A(sdone, n); A(ran, n); A(sched, SCHED_WORDS); A(pacc, NSHARD * PACC_STRIDE);
   W.claim_r[0] = W.claim; W.claim_r[1] = W.claim2;
   A(claim_r[2], ng); A(claim_r[3], ng); A(b_tgt, 4 * R);
   if (c.birth_method == 4) {
@@ -225,7 +225,7 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   w->d_W = w->d_Wv[0];
   w->validv[0] = w->validv[1] = false;
   const int64_t nb = (n + 255) / 256;
-  if ((rc = w->alloc(&w->d_totals, (size_t)(8 + 2 * nb)))) return rc;
+  if ((rc = w->alloc(&w->d_totals, (size_t)totals_words(nb)))) return rc;
   W.totals = w->d_totals;
   // the scheduler's tree: block counts, the top tree's levels (a strip tile
   // regrows them for the whole world at avgpu_tile_begin)
@@ -234,7 +234,7 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   while (W.tree_cap < nb) W.tree_cap <<= 1;
   if ((rc = w->alloc(&W.tree_scr, (size_t)(2 * W.tree_cap)))) return rc;
   if ((rc = w->alloc(&W.tree_cnt, (size_t)(2 * W.tree_cap)))) return rc;
-  if ((rc = w->alloc(&w->d_stats, (size_t)(45 + 24 * nb)))) return rc;
+  if ((rc = w->alloc(&w->d_stats, (size_t)stats_words(nb)))) return rc;
 #undef A
   w->has_test_buffers = test_buffers;
   // config scalars
@@ -398,7 +398,7 @@ avgpu_world* create_world(const avgpu_cfg* cfg, int device, int64_t n, bool test
   if (n <= 0) n = (int64_t)cfg->world_x * cfg->world_y;
   if (n <= 0 || n > (1ll << 30)) { delete w; fail(AVGPU_EINVAL, "bad cell count"); return nullptr; }
   if (hipStreamCreateWithFlags(&w->own_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipHostMalloc((void**)&w->h_pred, 4 * sizeof(long long), hipHostMallocMapped | hipHostMallocCoherent) !=
+      hipHostMalloc((void**)&w->h_pred, PRED_WORDS * sizeof(long long), hipHostMallocMapped | hipHostMallocCoherent) !=
           hipSuccess ||
       hipHostMalloc((void**)&w->h_stage, 2 * sizeof(DevWorld), hipHostMallocDefault) != hipSuccess ||
       hipEventCreateWithFlags(&w->ev_stage[0], hipEventDisableTiming) != hipSuccess ||
@@ -406,7 +406,7 @@ avgpu_world* create_world(const avgpu_cfg* cfg, int device, int64_t n, bool test
       hipHostGetDevicePointer((void**)&w->d_pred, w->h_pred, 0) != hipSuccess) {
     delete w; fail(AVGPU_EHIP, "stream/event creation failed"); return nullptr;
   }
-  w->h_pred[0] = w->h_pred[1] = w->h_pred[2] = w->h_pred[3] = 0;
+  for (int k = 0; k < PRED_WORDS; k++) w->h_pred[k] = 0;
   w->stream = w->own_stream;
   for (int i = 0; i < avgpu_world::RING; i++) {
     for (int k = 0; k <= NUM_CLASSES; k++)
@@ -962,11 +962,11 @@ static uint32_t step_key(const avgpu_world* w, int sub, int K) {
 // merit, allotment, class lists and the class-0 order; interpretation;
 // placement; the newborn pass.  own_totals: the picks come from the world's
 // own totals, and the last step's placement publishes the predictor; else
-// from the totals handed in in d_totals[0..1] (K = 1).
+// from the totals handed in in d_totals' first TOT_HANDED slots (K = 1).
 static int run_steps(avgpu_world* w, int K, bool own_totals, avgpu_update_stats* out) {
   for (int sub = 0; sub < K; sub++) {
     const uint32_t key = step_key(w, sub, K);
-    launch_world_begin(w->W, w->stream, w->d_totals, w->d_totals + 8, key, sub, K, own_totals);
+    launch_world_begin(w->W, w->stream, w->d_totals, w->d_totals + TOT_WORDS, key, sub, K, own_totals);
     if (sub == 0) after_resources_begin(w);
     HIPCHK(hipGetLastError());
     const int rc = interpret(w, AVGPU_MODE_WORLD, 0, w->W.n, true);
@@ -992,7 +992,7 @@ int avgpu_update_totals(avgpu_world* w, double* dev_totals) {
   int rc = ready(w);
   if (rc < 0) return rc;
   if (!dev_totals) return fail(AVGPU_EINVAL, "dev_totals is NULL");
-  launch_merit_total(w->W, w->stream, dev_totals, w->d_totals + 8);
+  launch_merit_total(w->W, w->stream, dev_totals, w->d_totals + TOT_WORDS);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1007,7 +1007,7 @@ int avgpu_update_run(avgpu_world* w, const double* dev_totals, avgpu_update_stat
   // picks (cMultiProcessWorld::CalculateUpdateSize) and its allotment; one
   // batch step (choose_k: handed-in totals)
   if (dev_totals != w->d_totals)
-    HIPCHK(hipMemcpyAsync(w->d_totals, dev_totals, 2 * sizeof(double), hipMemcpyDeviceToDevice, w->stream));
+    HIPCHK(hipMemcpyAsync(w->d_totals, dev_totals, TOT_HANDED * sizeof(double), hipMemcpyDeviceToDevice, w->stream));
   w->pred_pending = false;
   return run_steps(w, 1, false, out);
 }
@@ -1029,16 +1029,16 @@ int avgpu_run_update(avgpu_world* w, avgpu_update_stats* out) {
     // host polls that instead of an event on the stream (an event record
     // there left ~6 us of dead time per update before the next launch)
     const auto t0 = std::chrono::steady_clock::now();
-    while (__atomic_load_n(w->h_pred + 3, __ATOMIC_ACQUIRE) != w->pred_seq) {
+    while (__atomic_load_n(w->h_pred + PRED_SEQ, __ATOMIC_ACQUIRE) != w->pred_seq) {
       if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
         HIPCHK(hipStreamSynchronize(w->stream));   // a fault surfaces here
-        if (__atomic_load_n(w->h_pred + 3, __ATOMIC_ACQUIRE) != w->pred_seq)
+        if (__atomic_load_n(w->h_pred + PRED_SEQ, __ATOMIC_ACQUIRE) != w->pred_seq)
           return fail(AVGPU_EHIP, "the batch-step predictor was never published");
       }
     }
-    w->pred_acc = __atomic_load_n(w->h_pred + 0, __ATOMIC_ACQUIRE);
-    w->pred_n = __atomic_load_n(w->h_pred + 1, __ATOMIC_ACQUIRE);
-    w->pred_cnt = __atomic_load_n(w->h_pred + 2, __ATOMIC_ACQUIRE);
+    w->pred_acc = __atomic_load_n(w->h_pred + PRED_ACC, __ATOMIC_ACQUIRE);
+    w->pred_n = __atomic_load_n(w->h_pred + PRED_ORGS, __ATOMIC_ACQUIRE);
+    w->pred_cnt = __atomic_load_n(w->h_pred + PRED_DENSEST, __ATOMIC_ACQUIRE);
     w->pred_pending = false;
   }
   const int K = choose_k(w->cfg, w->pred_acc, w->pred_n, false, w->pred_cnt);
@@ -1239,7 +1239,7 @@ int avgpu_run_updates(avgpu_world* w, int n, avgpu_update_stats* last) {
 
 int avgpu_get_stats(avgpu_world* w, avgpu_update_stats* out) {
   if (!w || !out) return fail(AVGPU_EINVAL, "args");
-  double v[45];
+  double v[NSTAT];
   if (w->stats_stale) {
     launch_stats(w->W, w->stream, w->d_stats);
     HIPCHK(hipGetLastError());
@@ -1249,33 +1249,33 @@ int avgpu_get_stats(avgpu_world* w, avgpu_update_stats* out) {
   HIPCHK(hipStreamSynchronize(w->stream));
   memset(out, 0, sizeof(*out));
   out->update = w->update - 1;
-  out->num_organisms = (int64_t)v[0];
-  out->sum_merit = v[1];
-  out->sum_fitness = v[2];
-  out->sum_gestation = v[3];
-  out->sum_genome_length = v[4];
-  out->max_fitness = v[5];
-  out->ave_generation = v[0] > 0 ? v[6] / v[0] : 0.0;
-  for (int t = 0; t < AVGPU_NUM_LOGIC_TASKS; t++) out->task_orgs[t] = (int64_t)v[8 + t];
-  out->insts_executed = (int64_t)v[24];
-  out->deaths = (int64_t)v[25];
-  out->divides = (int64_t)v[26];
-  out->births = (int64_t)v[27];
-  out->births_dropped = (int64_t)v[28];
-  out->sum_mem_size = v[7];
-  out->cum_insts_executed = (int64_t)v[30];
-  out->cum_births = (int64_t)v[31];
-  out->slices = (int64_t)v[32];
-  out->lane_steps = (int64_t)v[33];
-  out->births_overwritten = (int64_t)v[34];
-  out->births_cancelled = (int64_t)v[35];
+  out->num_organisms = (int64_t)v[ST_ORGS];
+  out->sum_merit = v[ST_MERIT];
+  out->sum_fitness = v[ST_FITNESS];
+  out->sum_gestation = v[ST_GESTATION];
+  out->sum_genome_length = v[ST_GENOME_LEN];
+  out->max_fitness = v[ST_MAX_FITNESS];
+  out->ave_generation = v[ST_ORGS] > 0 ? v[ST_GENERATION] / v[ST_ORGS] : 0.0;
+  for (int t = 0; t < AVGPU_NUM_LOGIC_TASKS; t++) out->task_orgs[t] = (int64_t)v[ST_TASK0 + t];
+  out->insts_executed = (int64_t)v[ST_INSTS];
+  out->deaths = (int64_t)v[ST_DEATHS];
+  out->divides = (int64_t)v[ST_DIVIDES];
+  out->births = (int64_t)v[ST_BIRTHS];
+  out->births_dropped = (int64_t)v[ST_DROPPED];
+  out->sum_mem_size = v[ST_MEM_SIZE];
+  out->cum_insts_executed = (int64_t)v[ST_CUM_INSTS];
+  out->cum_births = (int64_t)v[ST_CUM_BIRTHS];
+  out->slices = (int64_t)v[ST_SLICES];
+  out->lane_steps = (int64_t)v[ST_LANESTEPS];
+  out->births_overwritten = (int64_t)v[ST_OVERWRITTEN];
+  out->births_cancelled = (int64_t)v[ST_CANCELLED];
   out->seed = w->cfg.seed;
-  out->insts_wasted = (int64_t)v[36];
-  memcpy(&out->sched_pred, v + 37, 8);        // (int64 bits)
-  memcpy(&out->sched_carry, v + 38, 8);
-  out->sched_pred_n = (int64_t)v[39];
-  memcpy(&out->sched_pred_cnt, v + 40, 8);
-  for (int q = 0; q < 4; q++) memcpy(&out->sched_pred_bins[q], v + 41 + q, 8);
+  out->insts_wasted = (int64_t)v[ST_WASTED];
+  memcpy(&out->sched_pred, v + ST_PRED, 8);        // (int64 bits)
+  memcpy(&out->sched_carry, v + ST_CARRY, 8);
+  out->sched_pred_n = (int64_t)v[ST_PRED_ORGS];
+  memcpy(&out->sched_pred_cnt, v + ST_PRED_DENSEST, 8);
+  for (int q = 0; q < 4; q++) memcpy(&out->sched_pred_bins[q], v + ST_QUARTER0 + q, 8);
   out->sub_steps = w->last_k;
   return 0;
 }
@@ -1502,8 +1502,8 @@ int avgpu_set_states(avgpu_world* w, int64_t first, int64_t count, const avgpu_c
 
 int avgpu_set_clock(avgpu_world* w, const avgpu_update_stats* last) {
   if (!w || !last) return fail(AVGPU_EINVAL, "args");
-  double v[2] = {(double)last->cum_insts_executed, (double)last->cum_births};
-  HIPCHK(hipMemcpyAsync(w->d_stats + 30, v, sizeof(v), hipMemcpyHostToDevice, w->stream));
+  double v[2] = {(double)last->cum_insts_executed, (double)last->cum_births};   // ST_CUM_INSTS, ST_CUM_BIRTHS
+  HIPCHK(hipMemcpyAsync(w->d_stats + ST_CUM_INSTS, v, sizeof(v), hipMemcpyHostToDevice, w->stream));
   // the running sums k_stats_final adds each update to
   const unsigned long long ci = (unsigned long long)last->cum_insts_executed;
   const unsigned long long cb = (unsigned long long)last->cum_births;
@@ -1538,16 +1538,17 @@ int avgpu_set_clock(avgpu_world* w, const avgpu_update_stats* last) {
   w->pred_cnt = std::max(std::max(last->sched_pred_bins[0], last->sched_pred_bins[1]),
                           std::max(last->sched_pred_bins[2], last->sched_pred_bins[3]));
   w->pred_pending = false;
-  const long long sv[5] = {0, 0, last->sched_carry, 0, 0};
+  long long sv[SCHED_UD + 1] = {};            // no step's carry, no UD yet
+  sv[SCHED_CARRY_REM] = last->sched_carry;
   HIPCHK(hipMemcpyAsync(w->W.sched, sv, sizeof(sv), hipMemcpyHostToDevice, w->stream));
   // the predictor into shard 0 (device.h pacc_sum), the other shards zero
   std::vector<long long> pa(NSHARD * PACC_STRIDE, 0);
-  pa[0] = last->sched_pred;
-  pa[1] = (long long)((uint64_t)last->sched_pred_bins[0] | ((uint64_t)last->sched_pred_bins[1] << 32));
-  pa[2] = (long long)((uint64_t)last->sched_pred_bins[2] | ((uint64_t)last->sched_pred_bins[3] << 32));
+  pa[PACC_WEIGHT] = last->sched_pred;
+  pa[PACC_Q01] = (long long)((uint64_t)last->sched_pred_bins[0] | ((uint64_t)last->sched_pred_bins[1] << 32));
+  pa[PACC_Q23] = (long long)((uint64_t)last->sched_pred_bins[2] | ((uint64_t)last->sched_pred_bins[3] << 32));
   HIPCHK(hipMemcpyAsync(w->W.pacc, pa.data(), pa.size() * sizeof(long long), hipMemcpyHostToDevice, w->stream));
   const double nv = (double)last->sched_pred_n;
-  HIPCHK(hipMemcpyAsync(w->d_totals + 1, &nv, sizeof(nv), hipMemcpyHostToDevice, w->stream));
+  HIPCHK(hipMemcpyAsync(w->d_totals + TOT_ORGS, &nv, sizeof(nv), hipMemcpyHostToDevice, w->stream));
   HIPCHK(hipStreamSynchronize(w->stream));
   return 0;
 }
@@ -1641,7 +1642,9 @@ int avgpu_stats_vector(avgpu_world* w, void** dev_ptr) {
 
 int avgpu_set_global_totals(avgpu_world* w, double total_merit, int64_t total_orgs) {
   if (!w) return fail(AVGPU_EINVAL, "NULL world");
-  double v[2] = {total_merit, (double)total_orgs};
+  double v[TOT_HANDED];
+  v[TOT_WEIGHT] = total_merit;
+  v[TOT_ORGS] = (double)total_orgs;
   HIPCHK(hipMemcpyAsync(w->d_totals, v, sizeof(v), hipMemcpyHostToDevice, w->stream));
   HIPCHK(hipStreamSynchronize(w->stream));
   w->use_global = true;
@@ -1742,7 +1745,7 @@ int avgpu_load_resources(avgpu_world* w, int nres, const avgpu_resource* res, in
     w->allocs.push_back(W.res_amount);
     HIPCHK(hipMalloc(&W.res_amount_alt, (size_t)AVGPU_MAX_RESOURCES * n * sizeof(double)));
     w->allocs.push_back(W.res_amount_alt);
-    HIPCHK(hipMalloc(&W.res_delta, (size_t)(n + 64) * sizeof(double)));   // + k_res_step's junk lanes
+    HIPCHK(hipMalloc(&W.res_delta, (size_t)res_delta_words(n) * sizeof(double)));
     w->allocs.push_back(W.res_delta);
   }
   if (nres && !W.cons) {   // each cell's consumption in a step (newborn credit)
@@ -1912,7 +1915,8 @@ int avgpu_tile_partials(avgpu_world* w, double* dev_out) {
   if (!dev_out) return fail(AVGPU_EINVAL, "dev_out is NULL");
   // a strip's first step of an update clears the update's counters, a later
   // step its queues only (the counts add up over the update)
-  launch_tile_partials(w->W, w->stream, dev_out, w->W.tiled ? (w->tile_sub_next == 0 ? 1 : 2) : 0);
+  launch_tile_partials(w->W, w->stream, dev_out,
+                       w->W.tiled ? (w->tile_sub_next == 0 ? RESET_COUNTS : RESET_QUEUES) : RESET_NONE);
   if (w->W.tiled) launch_resources_pack(w->W, w->stream);
   HIPCHK(hipGetLastError());
   return 0;
@@ -1925,21 +1929,21 @@ int avgpu_tile_steps(avgpu_world* w, const double* dev_gathered, int ntiles, int
   if (rc < 0) return rc;
   if (!dev_gathered || ntiles < 1 || !k_out) return fail(AVGPU_EINVAL, "gathered partials / k_out");
   const int64_t nb = (w->W.n + 255) / 256, stride = tile_part_stride(nb);
-  std::vector<double> tail((size_t)(6 * ntiles));
+  std::vector<double> tail((size_t)(TAIL_WORDS * ntiles));
   for (int k = 0; k < ntiles; k++)
-    HIPCHK(hipMemcpyAsync(tail.data() + 6 * k, dev_gathered + k * stride + 2 * nb, 6 * sizeof(double),
-                          hipMemcpyDeviceToHost, w->stream));
+    HIPCHK(hipMemcpyAsync(tail.data() + TAIL_WORDS * k, dev_gathered + k * stride + tile_tail_off(nb),
+                          TAIL_WORDS * sizeof(double), hipMemcpyDeviceToHost, w->stream));
   double n = 0.0;
-  HIPCHK(hipMemcpyAsync(&n, w->d_totals + 1, sizeof(double), hipMemcpyDeviceToHost, w->stream));
+  HIPCHK(hipMemcpyAsync(&n, w->d_totals + TOT_ORGS, sizeof(double), hipMemcpyDeviceToHost, w->stream));
   HIPCHK(hipStreamSynchronize(w->stream));
   long long sum = 0, bins[4] = {0, 0, 0, 0};
   for (int k = 0; k < ntiles; k++) {
     long long v;
-    memcpy(&v, tail.data() + 6 * k, 8);
+    memcpy(&v, tail.data() + TAIL_WORDS * k + TAIL_PRED, 8);
     sum += v;
     for (int q = 0; q < 4; q++) {
       long long c;
-      memcpy(&c, tail.data() + 6 * k + 2 + q, 8);
+      memcpy(&c, tail.data() + TAIL_WORDS * k + TAIL_QUARTER0 + q, 8);
       bins[q] += c;
     }
   }
@@ -2024,7 +2028,7 @@ int avgpu_last_step_insts(avgpu_world* w, int64_t* insts) {
   HIPCHK(hipMemcpyAsync(v.data(), w->W.counters, v.size() * 8, hipMemcpyDeviceToHost, w->stream));
   HIPCHK(hipStreamSynchronize(w->stream));
   unsigned long long s = 0;
-  for (int sh = 0; sh < NSHARD; sh++) s += v[sh * CNT_STRIDE + CNT_INSTS];
+  for (int sh = 0; sh < NSHARD; sh++) s += v[sh * CNT_STRIDE + AVGPU_CNT_INSTS];
   *insts = (int64_t)s;
   return 0;
 }

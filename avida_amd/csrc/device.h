@@ -141,15 +141,15 @@ struct DevWorld {
   // row 3 + k the organisms that spilled into class k during the update
   int32_t* class_list;   // [NUM_LISTS][n]
   int32_t* order;        // [n] class-0 order of a world update: cells of each SORT_WIN window by budget
-  int32_t* class_count;  // [8] entries of each list row
+  int32_t* class_count;  // [CLASS_COUNT_WORDS] entries of each list row
   unsigned long long* counters; // [16] insts, deaths, divides, births, dropped, ...
   // birth records.  Record r < n holds the first offspring that cell r's
   // parent produced in its slice (no atomics in the interpreter loop); records
   // n .. n+ocap-1 hold further offspring of one slice, reserved atomically.
-  // Queue entry i < b_count[0] is record b_list[i]; entry b_count[0] + j is
-  // record n + j (rec_of below).
+  // Queue entry i < b_count[BQ_PRIMARY] is record b_list[i]; entry
+  // b_count[BQ_PRIMARY] + j is record n + j (rec_of below).
   int64_t rcap;       // n + ocap
-  int32_t* b_count;   // [3] primary records listed, overflow records used, b_subs entries used
+  int32_t* b_count;   // [BQ_WORDS] (BQ_* below)
   int32_t* b_list;    // [n] primary record ids, appended per wave after the loop
   int32_t* b_parent;  // [rcap]
   uint32_t* b_seq;    // [rcap]
@@ -159,7 +159,7 @@ struct DevWorld {
   // variable-count divide-mutation edits of record r (only read when
   // seg_any): segment k holds b_pcnt[k][r] edit words from
   // b_subs[b_pofs[k][r]], applied at its place in Divide_DoMutations' order
-  // (SEG_* below); b_count[2] is the arena's fill of this update, scap its size
+  // (SEG_* below); b_count[BQ_SUBS] is the arena's fill of this update, scap its size
   int32_t* b_subs;    // [scap]
   int64_t scap;
   int32_t* b_pofs;    // [NSEG][rcap]
@@ -224,7 +224,7 @@ struct DevWorld {
   int32_t n_res, n_cellres, env_resources;   // env_resources: some reaction consumes a resource
   struct ResParam* res_param;   // [AVGPU_MAX_RESOURCES]
   double* res_amount;           // [n_spatial][n] spatial amounts (row = ResParam::slot)
-  double* res_delta;            // [n] rate scratch of the spatial step (+ 64: k_res_step's junk stores)
+  double* res_delta;            // [res_delta_words(n)] rate scratch of the spatial step
   double* res_global;           // [AVGPU_MAX_RESOURCES] global levels, fixed during an update
   unsigned long long* res_cons; // [AVGPU_MAX_RESOURCES] global consumption of the update, 2^-32 units
   avgpu_cell_resource* res_cells; // [n_cellres] CELL entries (cell ids are global)
@@ -335,23 +335,155 @@ struct DevWorld {
   // the batch step's newborns and sub-steps:
   int32_t* ran;       // [n] instructions each cell's organism ran in this step's main pass (k_allot zeroes)
   double* cons;       // [n_res][n] its depletable consumption in that pass (k_allot zeroes; env_resources)
-  // [1] this step's pick carry (newborn picks beyond
-  // their victims' leftovers, k_activate), [2] the carry not yet taken (taken
-  // at an update's first step), [4] the update's UD (AVE_TIME_SLICE x the
-  // organisms at its first step)
-  long long* sched;
+  long long* sched;   // [SCHED_WORDS] the scheduler's words (SCHED_* below)
   // the sub-step predictor of this step's main pass, sharded by block like
   // the counters (k_block_counts zeroes it): shard s at pacc[s * PACC_STRIDE]
-  // holds [0] its weight term (2^-20 mean weights), [1] its divide counts of
-  // quarters 0 | 1 << 32, [2] of quarters 2 | 3 << 32 (pacc_sum)
+  // (PACC_* below, pacc_sum)
   long long* pacc;
-  const double* totals;   // the step's totals (k_block_counts): [1] organisms, [2] weight total, [3] UD
+  const double* totals;   // the step's totals (k_block_counts; TOT_* below)
+};
+// (the interpreter loads the fields by scalar offset: none may move)
+static_assert(sizeof(DevWorld) == 1664, "DevWorld's size");
+
+// ---------------------------------------------------------------------------
+// The scratch vectors the update's kernels and the host hand each other.  Each
+// layout is stated here once: kernels, allocations and host copies take their
+// slots and sizes from these definitions, never from a number of their own.
+
+// The step totals (avgpu_world::d_totals = W.totals; k_block_counts writes
+// them).  A caller's buffer (avgpu_update_totals / avgpu_update_run) holds the
+// first TOT_HANDED slots only.
+enum {
+  TOT_WEIGHT = 0,   // the weight total: this world's own, or every world's handed in
+  TOT_ORGS = 1,     // the living organisms, likewise
+  TOT_HANDED = 2,   //   (slots a caller hands in / avgpu_update_totals writes)
+  TOT_DIV = 2,      // the weight total the allotment divides by
+  TOT_UD = 3,       // the update's UD
+  TOT_WORDS = 8     // then k_merit_partial's scratch: nb block partials, nb int32 alive counts
+};
+__host__ __device__ inline int64_t totals_words(int64_t nb) { return TOT_WORDS + 2 * nb; }
+
+// The scheduler's words W.sched
+enum {
+  SCHED_CARRY = 1,      // this step's pick carry (newborn picks beyond their victims' leftovers, k_activate)
+  SCHED_CARRY_REM = 2,  // the carry not yet taken (taken at an update's first step)
+  SCHED_UD = 4,         // the update's UD (AVE_TIME_SLICE x the organisms at its first step)
+  SCHED_WORDS = 12
 };
 
-// a strip's partials vector (avgpu_tile_partials): nb block partials, nb alive
-// counts, its sub-step predictor, its pick carry and its predictor's divide
-// counts by quarter (int64 bits)
-__host__ __device__ inline int64_t tile_part_stride(int64_t nb) { return 2 * nb + 6; }
+// A predictor shard's words (W.pacc; PACC_STRIDE words apart)
+enum {
+  PACC_WEIGHT = 0,   // its weight term (2^-20 mean weights)
+  PACC_Q01 = 1,      // its divide counts of quarters 0 | 1 << 32
+  PACC_Q23 = 2       // ... of quarters 2 | 3 << 32
+};
+
+// A strip's partials vector (avgpu_tile_partials): nb block partials, nb alive
+// counts (doubles), then a tail of int64 bits
+enum {
+  TAIL_PRED = 0,       // its sub-step predictor
+  TAIL_CARRY = 1,      // its pick carry
+  TAIL_QUARTER0 = 2,   // .. 5: its predictor's divide counts by quarter
+  TAIL_WORDS = 6
+};
+static_assert(TAIL_QUARTER0 + 4 == TAIL_WORDS, "a strip's tail ends with the four quarter counts");
+__host__ __device__ inline int64_t tile_tail_off(int64_t nb) { return 2 * nb; }
+__host__ __device__ inline int64_t tile_part_stride(int64_t nb) { return tile_tail_off(nb) + TAIL_WORDS; }
+
+// The predictor mailbox (coherent mapped host memory, avgpu_world::h_pred):
+// k_place_claim0 of an update's last step writes it, avgpu_run_update polls it
+enum {
+  PRED_ACC = 0,       // the predictor
+  PRED_ORGS = 1,      // the organisms it is relative to
+  PRED_DENSEST = 2,   // its densest quarter's divide count
+  PRED_SEQ = 3,       // the sequence number, stored last at system scope
+  PRED_WORDS = 4
+};
+
+// Birth-queue lengths W.b_count
+enum {
+  BQ_PRIMARY = 0,    // primary records listed in b_list
+  BQ_OVERFLOW = 1,   // overflow records used
+  BQ_SUBS = 2,       // b_subs entries used
+  BQ_WORDS = 3
+};
+// Rows of class_list / class_count: LIST_NEWBORN the newborn pass's class-0
+// organisms (k_activate), k = 1..3 the organisms k_allot put in class k,
+// LIST_SPILL + k those that spilled into class k
+enum { LIST_NEWBORN = 0, LIST_SPILL = 3, CLASS_COUNT_WORDS = 8 };
+static_assert(NUM_LISTS <= CLASS_COUNT_WORDS, "a length per list row");
+
+// k_res_step's idle lanes store into res_delta past the n cells: a wave's
+// worth of junk slots follows them
+#define RES_DELTA_TAIL 64
+__host__ __device__ inline int64_t res_delta_words(int64_t n) { return n + RES_DELTA_TAIL; }
+
+// The statistics vector (avgpu_world::d_stats; avgpu_stats_vector hands it
+// out as doubles): slots 0 .. NPART-1 the organisms' sums (k_stats_partial's
+// rows, reduced by k_stats_final), of which the first NUSED carry data; then
+// the update's counters and the scheduler's state (k_stats_final); then
+// k_stats_partial's rows, [NPART][nb]
+enum {
+  ST_ORGS = 0,          // living organisms
+  ST_MERIT = 1,         // sums over them: merit
+  ST_FITNESS = 2,
+  ST_GESTATION = 3,
+  ST_GENOME_LEN = 4,
+  ST_MAX_FITNESS = 5,   // (a maximum, not a sum)
+  ST_GENERATION = 6,
+  ST_MEM_SIZE = 7,
+  ST_TASK0 = 8,         // .. 16: organisms whose last gestation did task t
+  NUSED = ST_TASK0 + AVGPU_NUM_LOGIC_TASKS,   // .. NPART - 1: zero
+  NPART = 24,
+  ST_INSTS = 24,
+  ST_DEATHS = 25,
+  ST_DIVIDES = 26,
+  ST_BIRTHS = 27,
+  ST_DROPPED = 28,
+  ST_SPILLS = 29,
+  ST_CUM_INSTS = 30,    // over every update; ST_CUM_BIRTHS follows it (avgpu_set_clock writes the pair)
+  ST_CUM_BIRTHS = 31,
+  ST_SLICES = 32,
+  ST_LANESTEPS = 33,
+  ST_OVERWRITTEN = 34,
+  ST_CANCELLED = 35,
+  ST_WASTED = 36,
+  ST_PRED = 37,         // the sub-step predictor (int64 bits)
+  ST_CARRY = 38,        // the pick carry (int64 bits)
+  ST_PRED_ORGS = 39,    // the organisms the predictor is relative to
+  ST_PRED_DENSEST = 40, // its densest quarter's divide count (int64 bits)
+  ST_QUARTER0 = 41,     // .. 44: its divide counts by quarter (int64 bits)
+  NSTAT = 45
+};
+static_assert(NUSED <= NPART, "k_stats_partial's rows");
+static_assert(ST_INSTS == NPART, "the counters follow the partial sums");
+static_assert(ST_CUM_BIRTHS == ST_CUM_INSTS + 1, "avgpu_set_clock writes the pair");
+static_assert(ST_QUARTER0 + 4 == NSTAT, "the statistics vector ends with the four quarter counts");
+__host__ __device__ inline int64_t stats_words(int64_t nb) { return NSTAT + (int64_t)NPART * nb; }
+
+// Integer-coded kernel arguments
+// k_merit_partial's `reset`: what its block 0 zeroes first
+enum {
+  RESET_NONE = 0,
+  RESET_COUNTS = 1,   // the update's counters, the birth-queue and class-list lengths
+  RESET_QUEUES = 2    // a later step of the update: the queue and list lengths only
+};
+// k_block_counts' `mode` (world.hip): where the tree's leaves and the totals come from
+enum {
+  BC_OWN = 0,         // this world's partials and totals
+  BC_GATHERED = 1,    // a strip: every strip's gathered partials vectors
+  BC_HANDED_IN = 2,   // this world's partials, the totals of every world handed in
+  BC_TOTALS_ONLY = 3  // this world's {weight total, organisms} out, nothing else
+};
+// k_activate's `fused`
+enum { ACT_WORLD = 1 /* single world: resolves round 3 itself */, ACT_STRIP = 2 /* strip: its own winners */ };
+// launch_tile_place's `phase` (avgpu_tile_place's numbers), in the order of an update
+enum { TP_ROUND = 0, TP_CLAIM0 = 3, TP_PACK = 1, TP_ACTIVATE = 2 };
+// k_interpret's `sorted_arg` bits
+enum {
+  KI_SORTED = 1,   // the class-0 sweep follows the budget-sorted windows
+  KI_PRED = 2      // a world update's main pass: its slices add the sub-step predictor
+};
 // owner of a cell won by a neighbouring strip's offspring in round k at birth time t
 #define REMOTE_OWNER(k, t) (-2 - ((k) + 4 * (int)(t)))
 // halo buffer: per round parity X u64 claims on the receiver's edge row and X
@@ -375,29 +507,6 @@ __host__ __device__ inline int64_t record_bytes(int x, int64_t arena) {
   return (int64_t)sizeof(HaloHdr) + (int64_t)x * (int64_t)sizeof(HaloRec) + arena;
 }
 
-// counters[] slots
-#define CNT_INSTS 0
-#define CNT_DEATHS 1
-#define CNT_DIVIDES 2
-#define CNT_BIRTHS 3
-#define CNT_DROPPED 4
-#define CNT_SPILLS 5
-#define CNT_SLICES 6
-#define CNT_LANESTEPS 7   /* 64 x the longest lane of each wave: lane efficiency = insts / this */
-#define CNT_C0_SLICES 8   /* slices run by the class-0 interpreter launch */
-#define CNT_C0_SITES 9    /* tape sites it staged in + wrote back (sum of M at entry and exit) */
-// slots 10..17: AVGPU_PHASE_CLOCKS diagnostic builds only (s_memtime per wave)
-#define CNT_CLK_STAGE 10
-#define CNT_CLK_LOOP 11
-#define CNT_CLK_WB 12
-#define CNT_ITERS 13      /* loop iterations of the wave */
-#define CNT_IT_FAST 14    /* iterations in which some lane took the branch-free block */
-#define CNT_IT_COPY 15    /* ... the h-copy block */
-#define CNT_IT_SLOW 16    /* ... the switch */
-#define CNT_WAVES 17
-#define CNT_HALO_SENT 18  /* offspring shipped to a neighbouring tile */
-#define CNT_HALO_LOST 19  /* offspring lost to a full halo arena (counted in DROPPED too) */
-#define CNT_REC_OVER 20   /* RECORDED draws past the end of the stream */
 // variable-count edit segments of a birth record, in the order applied:
 // e0 (slip) or, with a data fill (SLIP_FILL_MODE 2 / 3), the one-shot slip as
 // a segment, Poisson slips, per-site slips (two words each with a data fill:
@@ -408,19 +517,8 @@ __host__ __device__ inline int64_t record_bytes(int x, int64_t arena) {
 // mutations.  Data fills (a slip's or translocation's L codes / source
 // sites) sit in the same arena, reserved per event.
 enum { SEG_OSLIP = 0, SEG_PSLIP, SEG_SSLIP, SEG_TTRANS, SEG_PTRANS, SEG_STRANS, SEG_PMUT, SEG_PINS, SEG_PDEL, SEG_SMUT, SEG_SINS, SEG_SDEL, SEG_SUNI, NSEG };
-#define CNT_SUB_OVERFLOW 22   /* DIV_MUT_PROB substitutions that found the b_subs arena full (must stay 0) */
-#define CNT_OVERSIZE 21   /* offspring a slip grew past AVGPU_MAX_GENOME (counted in DROPPED too) */
-#define CNT_MEM_CAP 23    /* copy insertions past AVGPU_MAX_GENOME sites / removals from one site (skipped) */
-#define CNT_OVERWRITTEN 24  /* offspring placed, then killed by a later birth into the same cell this update */
-#define CNT_CANCELLED 25  /* records whose parent's cell got an offspring before their divide (never placed) */
-#define CNT_BAD_RECORD 26 /* record / cell fields out of range where used as an index (guarded; must be 0) */
-#define CNT_WASTED 27     /* instructions replaced organisms ran after their newborns' birth times */
-#define CNT_STEPS 28      /* batch steps (k_block_counts, one per step) */
-// 32..37: AVGPU_PHASE_CLOCKS loop cycles by block (decode, fast, copy, switch,
-// wave phase, advance); 38..43: slow-switch cycles in pop, push, IO, h-alloc,
-// h-divide, h-search/if-label
-#define CNT_CB0 32
-#define CNT_CASE0 38
+// The slots of counters[] are the public enum avgpu_counter (avida_gpu.h),
+// the one list of them.
 // Counters are sharded over NSHARD lines (CNT_STRIDE x u64 each) so that the
 // per-wave adds of a 16K-wave launch do not serialise on one L2 address; they
 // are cleared every update, and counters[CNT_CUM_BASE + k] accumulates slot k
@@ -439,23 +537,23 @@ __device__ __forceinline__ long long pacc_sum(const DevWorld& W, int k) {
 }
 // quarter k's divide count
 __device__ __forceinline__ long long quarter_count(const DevWorld& W, int k) {
-  return (long long)(((unsigned long long)pacc_sum(W, 1 + (k >> 1)) >> (32 * (k & 1))) & 0xFFFFFFFFull);
+  return (long long)(((unsigned long long)pacc_sum(W, PACC_Q01 + (k >> 1)) >> (32 * (k & 1))) & 0xFFFFFFFFull);
 }
 __device__ __forceinline__ long long densest_quarter(const DevWorld& W) {
   return max(max(quarter_count(W, 0), quarter_count(W, 1)), max(quarter_count(W, 2), quarter_count(W, 3)));
 }
-#define CNT_CUM_INSTS (CNT_CUM_BASE + CNT_INSTS)
-#define CNT_CUM_BIRTHS (CNT_CUM_BASE + CNT_BIRTHS)
+#define CNT_CUM_INSTS (CNT_CUM_BASE + AVGPU_CNT_INSTS)
+#define CNT_CUM_BIRTHS (CNT_CUM_BASE + AVGPU_CNT_BIRTHS)
 // 1 once this update's counts are in the running sums (k_stats_final); 0 after
 // reset_counts_block, which folds them in itself when statistics were skipped
 #define CNT_CUM_FLAG (CNT_CUM_BASE + CNT_STRIDE - 1)
 
 __device__ __forceinline__ int queue_len(const DevWorld& W) {
-  const int64_t n = (int64_t)W.b_count[0] + (int64_t)min(W.b_count[1], (int)(W.rcap - W.n));
+  const int64_t n = (int64_t)W.b_count[BQ_PRIMARY] + (int64_t)min(W.b_count[BQ_OVERFLOW], (int)(W.rcap - W.n));
   return (int)n;
 }
 __device__ __forceinline__ int64_t rec_of(const DevWorld& W, int64_t i) {
-  const int p = W.b_count[0];
+  const int p = W.b_count[BQ_PRIMARY];
   return i < p ? (int64_t)W.b_list[i] : W.n + (i - p);
 }
 
@@ -784,9 +882,9 @@ void launch_age_tick(const DevWorld& W, hipStream_t s);
 // resources step and the update's counters are reset at sub 0 only; the key
 // of the scheduler's node draws is update x nsub + sub (the caller's `update`)
 // own_totals: the picks come from this world's own totals (k_block_counts
-// mode 0); else from the totals handed in in d_totals[0..1] (avgpu_update_totals
+// BC_OWN); else from the totals handed in in d_totals' TOT_WEIGHT, TOT_ORGS (avgpu_update_totals
 // + an all-reduce of every world's {total weight, organisms}), this world's
-// share by cMultiProcessWorld's formula (mode 2)
+// share by cMultiProcessWorld's formula (BC_HANDED_IN)
 void launch_world_begin(const DevWorld& W, hipStream_t s, double* d_totals, double* d_scratch, uint32_t update,
                         int sub, int nsub, bool own_totals);
 // a sub-update's share of the update's picks n (oracle sub_share)

@@ -323,7 +323,7 @@ __host__ __device__ constexpr int tape_stride(int S) { return S == CLASS0_SIZE ?
 // merit) from that point on, in mean weights, 2^-20 fixed point.
 __device__ __forceinline__ long long pred_term(const DevWorld& W, int cell, int tu, int gs, int blen, int dcop,
                                                int dexe, double bonus, int& q) {
-  const double total = W.totals[2], n = W.totals[1];
+  const double total = W.totals[TOT_DIV], n = W.totals[TOT_ORGS];
   if (!(total > 0.0) || !(n > 0.0)) return 0;
   const double wbar = __ddiv_rn(total, n);
   const double wi = W.merit[cell];
@@ -453,9 +453,9 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
       M = W.mem_size[cell];
     }
   } else if (NB && cls == 0) {
-    // the newborn pass's class-0 organisms: list row 0 (k_activate)
+    // the newborn pass's class-0 organisms: list row LIST_NEWBORN (k_activate)
     const int64_t idx = chunk * 64 + lane;
-    if (idx < W.class_count[0]) {
+    if (idx < W.class_count[LIST_NEWBORN]) {
       cell = W.class_list[idx];
       M = W.mem_size[cell];
     }
@@ -961,7 +961,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
                   M = Mn;
                 }
               }
-              if (ncap) count_add(W, CNT_MEM_CAP, (unsigned long long)ncap);
+              if (ncap) count_add(W, AVGPU_CNT_MEM_CAP, (unsigned long long)ncap);
             }
           }
         }
@@ -1514,8 +1514,8 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
               // overflows below)
               auto preserve = [&](int k, int n) {
                 if (n > 0 && mode == AVGPU_MODE_WORLD)
-                  pofs[k] = (int64_t)__atomic_load_n(W.b_count + 2, __ATOMIC_RELAXED) >= W.scap
-                                ? (int)W.scap : atomicAdd(W.b_count + 2, n);
+                  pofs[k] = (int64_t)__atomic_load_n(W.b_count + BQ_SUBS, __ATOMIC_RELAXED) >= W.scap
+                                ? (int)W.scap : atomicAdd(W.b_count + BQ_SUBS, n);
               };
               auto pput = [&](int k, int i, int ew) {
                 if (mode == AVGPU_MODE_WORLD && pofs[k] >= 0 && (int64_t)pofs[k] + i < W.scap) W.b_subs[pofs[k] + i] = ew;
@@ -1538,8 +1538,8 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
                 const int nbw = kind == 2 ? 0 : (L + 31) >> 5;
                 int off = -1;
                 if (mode == AVGPU_MODE_WORLD) {
-                  if ((int64_t)__atomic_load_n(W.b_count + 2, __ATOMIC_RELAXED) < W.scap) {
-                    const int o = atomicAdd(W.b_count + 2, L + nbw);
+                  if ((int64_t)__atomic_load_n(W.b_count + BQ_SUBS, __ATOMIC_RELAXED) < W.scap) {
+                    const int o = atomicAdd(W.b_count + BQ_SUBS, L + nbw);
                     if ((int64_t)o + L + nbw <= W.scap) off = o;
                   }
                   if (off < 0) ftrunc = true;
@@ -1761,14 +1761,14 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
               }
               // a segment that did not fit the arena (its edits were not all
               // written): the offspring cannot be rebuilt, so it is dropped
-              // (counted in CNT_SUB_OVERFLOW and CNT_DROPPED; tests require 0)
+              // (counted in AVGPU_CNT_SUB_OVERFLOW and AVGPU_CNT_DROPPED; tests require 0)
               bool truncated = false;
-              if (ftrunc) { count_add(W, CNT_SUB_OVERFLOW, 1ull); truncated = true; }   // a fill found the arena full
+              if (ftrunc) { count_add(W, AVGPU_CNT_SUB_OVERFLOW, 1ull); truncated = true; }   // a fill found the arena full
               if (segs && mode == AVGPU_MODE_WORLD)
 #pragma unroll
                 for (int k = 0; k < NSEG; k++)
                   if (pcnt[k] > 0 && ((int64_t)pofs[k] < 0 || (int64_t)pofs[k] + pcnt[k] > W.scap)) {
-                    count_add(W, CNT_SUB_OVERFLOW, (unsigned long long)pcnt[k]);
+                    count_add(W, AVGPU_CNT_SUB_OVERFLOW, (unsigned long long)pcnt[k]);
                     truncated = true;
                   }
               // (the parent's own mutations -- Divide_DoMutations' last draws,
@@ -1785,7 +1785,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
               } else if (mode == AVGPU_MODE_WORLD) {
               rec = cell;
               if (prim) {
-                rec = (int)min((int64_t)W.n + atomicAdd(W.b_count + 1, 1), W.rcap);
+                rec = (int)min((int64_t)W.n + atomicAdd(W.b_count + BQ_OVERFLOW, 1), W.rcap);
                 if (rec >= W.rcap) { rec = -1; ndrop++; }
               }
               prim = true;
@@ -1914,10 +1914,10 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
               // the sorted sites sit in the last 4 * nins bytes of the slot
               // and the parent grows below them: M + 5 * nins <= S.  A parent
               // near its slot's end keeps the insertions that fit (the rest
-              // counted in CNT_MEM_CAP; the oracle has no slot, tests require 0)
+              // counted in AVGPU_CNT_MEM_CAP; the oracle has no slot, tests require 0)
               const int nfit = (Scap - M) / 5;
               if (nins > nfit) {
-                count_add(W, CNT_MEM_CAP, (unsigned long long)(nins - nfit));
+                count_add(W, AVGPU_CNT_MEM_CAP, (unsigned long long)(nins - nfit));
                 nins = nfit;
               }
               if (nins > 0) {
@@ -2064,10 +2064,10 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
       // a class-0 world slice continues in the same wave (k_interpret), the
       // others in the spill row of class cls+1
       if (!(C0W && cls == 0)) {
-        const int slot = atomicAdd(&W.class_count[3 + cls + 1], 1);
-        W.class_list[(int64_t)(3 + cls + 1) * N + slot] = cell;
+        const int slot = atomicAdd(&W.class_count[LIST_SPILL + cls + 1], 1);
+        W.class_list[(int64_t)(LIST_SPILL + cls + 1) * N + slot] = cell;
       }
-      count_add(W, CNT_SPILLS, 1ull);
+      count_add(W, AVGPU_CNT_SPILLS, 1ull);
     }
   }
   // tapes back to HBM: the same lane-linear image, one granule per lane
@@ -2093,7 +2093,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     const unsigned long long bm = __ballot(fresh);
     if (bm) {
       int base = 0;
-      if (lane == 0) base = atomicAdd(W.b_count, (int)__popcll(bm));
+      if (lane == 0) base = atomicAdd(W.b_count + BQ_PRIMARY, (int)__popcll(bm));
       base = __shfl(base, 0);
       if (fresh) W.b_list[base + (int)__popcll(bm & ((1ull << lane) - 1ull))] = cell;
     }
@@ -2107,14 +2107,14 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
       pt = pred_term(W, cell, tu, gs, blen, dcop, dexe, bonus, q);
     for (int off = 32; off > 0; off >>= 1) pt += __shfl_xor(pt, off);
     unsigned long long* pa = reinterpret_cast<unsigned long long*>(W.pacc) + (blockIdx.x & (NSHARD - 1)) * PACC_STRIDE;
-    if (lane == 0 && pt) atomicAdd(pa, (unsigned long long)pt);
+    if (lane == 0 && pt) atomicAdd(pa + PACC_WEIGHT, (unsigned long long)pt);
     // the quarter counts, two per 64-bit word: two atomics per wave
     const unsigned long long q01 = (unsigned long long)__popcll(__ballot(q == 0)) |
                                    ((unsigned long long)__popcll(__ballot(q == 1)) << 32);
     const unsigned long long q23 = (unsigned long long)__popcll(__ballot(q == 2)) |
                                    ((unsigned long long)__popcll(__ballot(q == 3)) << 32);
-    if (lane == 0 && q01) atomicAdd(pa + 1, q01);
-    if (lane == 0 && q23) atomicAdd(pa + 2, q23);
+    if (lane == 0 && q01) atomicAdd(pa + PACC_Q01, q01);
+    if (lane == 0 && q23) atomicAdd(pa + PACC_Q23, q23);
   }
   // counters: one atomic per wave
   unsigned long long e = (unsigned long long)executed;
@@ -2136,16 +2136,16 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     sites += __shfl_down(sites, off);
   }
   if (lane == 0) {
-    count_add(W, CNT_LANESTEPS, 64ull * (unsigned long long)mxe);   // issued lane-steps
-    count_add(W, CNT_INSTS, e);
-    if (dead) count_add(W, CNT_DEATHS, (unsigned long long)dead);
-    if (dv) count_add(W, CNT_DIVIDES, (unsigned long long)dv);
-    if (ndrop) count_add(W, CNT_DROPPED, (unsigned long long)ndrop);
-    if (nover) count_add(W, CNT_OVERSIZE, (unsigned long long)nover);
-    if (REC && nrover) count_add(W, CNT_REC_OVER, (unsigned long long)nrover);
+    count_add(W, AVGPU_CNT_LANESTEPS, 64ull * (unsigned long long)mxe);   // issued lane-steps
+    count_add(W, AVGPU_CNT_INSTS, e);
+    if (dead) count_add(W, AVGPU_CNT_DEATHS, (unsigned long long)dead);
+    if (dv) count_add(W, AVGPU_CNT_DIVIDES, (unsigned long long)dv);
+    if (ndrop) count_add(W, AVGPU_CNT_DROPPED, (unsigned long long)ndrop);
+    if (nover) count_add(W, AVGPU_CNT_OVERSIZE, (unsigned long long)nover);
+    if (REC && nrover) count_add(W, AVGPU_CNT_REC_EXHAUSTED, (unsigned long long)nrover);
     if (S == CLASS0_SIZE && !NB) {   // everything the class-0 launch runs: its windows, list blocks, in-wave spills
-      count_add(W, CNT_C0_SLICES, (unsigned long long)sl);
-      count_add(W, CNT_C0_SITES, (unsigned long long)sites);
+      count_add(W, AVGPU_CNT_C0_SLICES, (unsigned long long)sl);
+      count_add(W, AVGPU_CNT_C0_SITES, (unsigned long long)sites);
     }
   }
 #ifdef AVGPU_PHASE_CLOCKS
@@ -2157,16 +2157,16 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
       it_slow = max(it_slow, __shfl_down(it_slow, off));
     }
     if (lane == 0 && cls == 0) {
-      count_add(W, CNT_CLK_STAGE, clk1 - clk0);
-      count_add(W, CNT_CLK_LOOP, clk2 - clk1);
-      count_add(W, CNT_CLK_WB, clk3 - clk2);
-      count_add(W, CNT_ITERS, (unsigned long long)it_loop);
-      count_add(W, CNT_IT_FAST, (unsigned long long)it_fast);
-      count_add(W, CNT_IT_COPY, (unsigned long long)it_copy);
-      count_add(W, CNT_IT_SLOW, (unsigned long long)it_slow);
-      count_add(W, CNT_WAVES, 1ull);
-      for (int k = 0; k < 6; k++) count_add(W, CNT_CB0 + k, cb[k]);
-      for (int k = 0; k < 10; k++) count_add(W, CNT_CASE0 + k, cc[k]);
+      count_add(W, AVGPU_CNT_CLK_STAGE, clk1 - clk0);
+      count_add(W, AVGPU_CNT_CLK_LOOP, clk2 - clk1);
+      count_add(W, AVGPU_CNT_CLK_WB, clk3 - clk2);
+      count_add(W, AVGPU_CNT_ITERS, (unsigned long long)it_loop);
+      count_add(W, AVGPU_CNT_IT_FAST, (unsigned long long)it_fast);
+      count_add(W, AVGPU_CNT_IT_COPY, (unsigned long long)it_copy);
+      count_add(W, AVGPU_CNT_IT_SLOW, (unsigned long long)it_slow);
+      count_add(W, AVGPU_CNT_WAVES, 1ull);
+      for (int k = 0; k < 6; k++) count_add(W, AVGPU_CNT_CB0 + k, cb[k]);
+      for (int k = 0; k < 10; k++) count_add(W, AVGPU_CNT_CASE0 + k, cc[k]);
     }
   }
 #endif
@@ -2185,9 +2185,9 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
 #define MIX_B3 8
 #define MIX_BLOCKS (MIX_B1 + MIX_B2 + MIX_B3)
 static_assert(MIX_BLOCKS % 8 == 0, "class 0's XCD mapping needs whole rounds of 8 blocks");
-// `sorted`: bit 0 the class-0 sweep follows the budget-sorted windows, bit 1
-// a world update's main pass (its slices add the sub-step predictor); NB: the
-// newborn pass (class 0 over list row 0, a grid-stride)
+// `sorted_arg`: KI_SORTED the class-0 sweep follows the budget-sorted windows,
+// KI_PRED a world update's main pass (its slices add the sub-step predictor);
+// NB: the newborn pass (class 0 over list row LIST_NEWBORN, a grid-stride)
 template <int S, bool REC, bool C0W = false, bool SIMPLE = false, bool DEF = false, bool RES = false, bool NB = false>
 __global__ __launch_bounds__(64, (S == CLASS0_SIZE) ? 2 : 1) void k_interpret(const DevWorld* __restrict__ Wp, int cls, int row, int mode,
                                                   int64_t first, int64_t count, int sorted_arg, int lpw, int nmix = 0) {
@@ -2196,8 +2196,8 @@ __global__ __launch_bounds__(64, (S == CLASS0_SIZE) ? 2 : 1) void k_interpret(co
   constexpr int STK = (S == CLASS0_SIZE) ? 0 : 2 * AVGPU_STACK_SIZE * 64;
   constexpr int TAB = (S == CLASS0_SIZE) ? 0 : TAB_WORDS;     // class 0: tapes only
   __shared__ __attribute__((aligned(16))) uint32_t lds32[64 * tape_stride(S) / 4 + STK + TAB];
-  const int sorted = sorted_arg & 1;
-  const bool pred = (sorted_arg & 2) != 0;
+  const int sorted = sorted_arg & KI_SORTED;
+  const bool pred = (sorted_arg & KI_PRED) != 0;
   if (cls == 0) {
     if (S == CLASS0_SIZE && C0W && (int)blockIdx.x < nmix) {
       const int b = blockIdx.x;
@@ -2249,8 +2249,8 @@ __global__ __launch_bounds__(64, (S == CLASS0_SIZE) ? 2 : 1) void k_interpret(co
       }
     };
     if (NB) {
-      // the newborn pass: a grid-stride over list row 0
-      const int ncount = Wp->class_count[0];
+      // the newborn pass: a grid-stride over list row LIST_NEWBORN
+      const int ncount = Wp->class_count[LIST_NEWBORN];
       for (int64_t chunk = bx; chunk * 64 < ncount; chunk += gx) {
         run_chunk(chunk);
         __syncthreads();
@@ -2561,12 +2561,12 @@ __global__ __launch_bounds__(64, 1) void k_serial_update(const DevWorld* __restr
   }
   if (lane == 0) {
     W.grng[2] = gct;
-    count_add(W, CNT_INSTS, picks);
-    if (deaths) count_add(W, CNT_DEATHS, deaths);
-    if (divides) count_add(W, CNT_DIVIDES, divides);
-    if (births) count_add(W, CNT_BIRTHS, births);
-    if (dropped) count_add(W, CNT_DROPPED, dropped);
-    if (over) count_add(W, CNT_REC_OVER, over);
+    count_add(W, AVGPU_CNT_INSTS, picks);
+    if (deaths) count_add(W, AVGPU_CNT_DEATHS, deaths);
+    if (divides) count_add(W, AVGPU_CNT_DIVIDES, divides);
+    if (births) count_add(W, AVGPU_CNT_BIRTHS, births);
+    if (dropped) count_add(W, AVGPU_CNT_DROPPED, dropped);
+    if (over) count_add(W, AVGPU_CNT_REC_EXHAUSTED, over);
   }
 }
 
@@ -2640,14 +2640,14 @@ static void launch_interpret(Interp v, unsigned grid, hipStream_t s, const DevWo
 // over the organisms k_activate listed -- class 0 from list row 0 by a
 // grid-stride of NB_BLOCKS blocks, the list classes in its leading blocks,
 // then the spill rows.  A world update's main pass (sorted) adds the sub-step
-// predictor (bit 1 of the kernels' `sorted` argument).
+// predictor (KI_PRED of the kernels' `sorted_arg`).
 #define NB_BLOCKS 2048
 template <bool REC, bool NB>
 static void launch_classes(const DevWorld& W, const DevWorld* dW, int mode, hipStream_t s,
                            int64_t first, int64_t count, int* launches, hipEvent_t* after_class, bool sorted) {
   const bool c0w = mode == AVGPU_MODE_WORLD;
-  const int pfl = (!NB && sorted && c0w) ? 2 : 0;
-  const int srt = ((!NB && sorted && first == 0 && count == W.n) ? 1 : 0) | pfl;
+  const int pfl = (!NB && sorted && c0w) ? KI_PRED : 0;
+  const int srt = ((!NB && sorted && first == 0 && count == W.n) ? KI_SORTED : 0) | pfl;
   const bool tall = class_timing_all();
   const unsigned blocks = NB ? (unsigned)NB_BLOCKS : (unsigned)((count + 63) / 64);
   if (blocks == 0) {

@@ -307,6 +307,7 @@ __global__ __launch_bounds__(256) void k_res_step(DevWorld W, ResIds ids, int ng
   // into res_delta's tail -- so the memory-counter waits stay exact (stores
   // count too on this generation) and a load is waited for two iterations
   // after it was issued.
+  static_assert(64 <= RES_DELTA_TAIL, "res_delta's tail holds a junk slot for each of the wave's 64 lanes");
   double* junk = W.res_delta + W.n + lane;
   // four row registers in fixed roles over a 4-row unrolled step, so a load
   // lands in its own register and no copy waits for it

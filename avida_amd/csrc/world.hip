@@ -367,8 +367,8 @@ __global__ void k_classify_uniform(DevWorld W, int64_t first, int64_t count, con
 // to the running sums here instead of in k_stats_final.  One block, >= 256
 // threads; the caller's condition is block-uniform.
 __device__ __forceinline__ void reset_queues_block(const DevWorld& W) {
-  if (threadIdx.x < 3) W.b_count[threadIdx.x] = 0;
-  if (threadIdx.x < 8) W.class_count[threadIdx.x] = 0;
+  if (threadIdx.x < BQ_WORDS) W.b_count[threadIdx.x] = 0;
+  if (threadIdx.x < CLASS_COUNT_WORDS) W.class_count[threadIdx.x] = 0;
 }
 __device__ __forceinline__ void reset_counts_block(const DevWorld& W) {
   constexpr int NG = 256 / CNT_STRIDE;
@@ -394,13 +394,13 @@ __device__ __forceinline__ void reset_counts_block(const DevWorld& W) {
     else if (t) W.counters[CNT_CUM_BASE + threadIdx.x] += t;
   }
   for (int i = threadIdx.x; i < NSHARD * CNT_STRIDE; i += blockDim.x) W.counters[i] = 0ull;
-  if (threadIdx.x < 3) W.b_count[threadIdx.x] = 0;
-  if (threadIdx.x < 8) W.class_count[threadIdx.x] = 0;
+  if (threadIdx.x < BQ_WORDS) W.b_count[threadIdx.x] = 0;
+  if (threadIdx.x < CLASS_COUNT_WORDS) W.class_count[threadIdx.x] = 0;
 }
 
-// reset 1: block 0 also zeroes the update's counters, birth-queue and class-list
+// RESET_COUNTS: block 0 also zeroes the update's counters, birth-queue and class-list
 // lengths (k_reset_counts' work; the previous update's statistics have read them);
-// reset 2 (a later sub-update): the queue and list lengths only, the counters
+// RESET_QUEUES (a later sub-update): the queue and list lengths only, the counters
 // go on adding up the update
 // One wave per 256-cell block b (partial[b]): the pairwise tree of strides
 // 128, 64, ..., 1 (s[t] += s[t + stride]), the oracle's tree_merit_sum order.
@@ -409,16 +409,17 @@ __device__ __forceinline__ void reset_counts_block(const DevWorld& W) {
 // same order, without the LDS tree's 8 barriers.  Four blocks per workgroup.
 __global__ __launch_bounds__(256) void k_merit_partial(DevWorld W, double* partial, int32_t* alive_partial,
                                                        double* alive_d, int reset) {
-  if (reset == 1 && blockIdx.x == 0) reset_counts_block(W);
-  if (reset == 2 && blockIdx.x == 0) reset_queues_block(W);
+  if (reset == RESET_COUNTS && blockIdx.x == 0) reset_counts_block(W);
+  if (reset == RESET_QUEUES && blockIdx.x == 0) reset_queues_block(W);
   // a strip's partials end with its last step's predictor, pick carry and
-  // divide counts by quarter (the oracle's orc_tile_partials; summed on every
-  // strip after the gather)
-  if (alive_d && blockIdx.x == 0 && threadIdx.x < 6) {
+  // divide counts by quarter (the TAIL_* words; the oracle's orc_tile_partials;
+  // summed on every strip after the gather)
+  if (alive_d && blockIdx.x == 0 && threadIdx.x < TAIL_WORDS) {
     const int64_t nbl = (W.n + 255) / 256;
-    const long long v = threadIdx.x == 0 ? pacc_sum(W, 0)
-                        : (threadIdx.x == 1 ? W.sched[1] : quarter_count(W, (int)threadIdx.x - 2));
-    partial[2 * nbl + threadIdx.x] = __longlong_as_double(v);
+    const long long v = threadIdx.x == TAIL_PRED ? pacc_sum(W, PACC_WEIGHT)
+                        : (threadIdx.x == TAIL_CARRY ? W.sched[SCHED_CARRY]
+                                                     : quarter_count(W, (int)threadIdx.x - TAIL_QUARTER0));
+    partial[tile_tail_off(nbl) + threadIdx.x] = __longlong_as_double(v);
   }
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -456,14 +457,15 @@ __global__ __launch_bounds__(256) void k_merit_partial(DevWorld W, double* parti
 //
 // k_block_counts: heap-ordered top tree in tree_scr (node h = (1 << l) + i,
 // children 2h, 2h + 1; leaves at P + block, zero-padded to P = 2^L), built
-// bottom up, split top down in tree_cnt.  mode 0: this world's partials
-// (part doubles, alive int32); mode 1: a strip's gathered vector (tile k's
-// block j at gathered[k * 2 nb + j], its alive count nb after); mode 2: this
-// world's partials with the totals of every world handed in (totals[0..1]:
-// cMultiProcessWorld::CalculateUpdateSize, main/cMultiProcessWorld.cc:
-// 396-405 -- this world's picks = (int)((local / total) * AVE_TIME_SLICE *
-// N_total)); mode 3: the totals only (totals[0..1] = root, N).
-// totals[2] = the weight total INTEGRATED divides by, totals[3] = UD.
+// bottom up, split top down in tree_cnt.  BC_OWN: this world's partials
+// (part doubles, alive int32); BC_GATHERED: a strip's gathered vector (tile
+// k's block j at gathered[k * tile_part_stride(nb) + j], its alive count nb
+// after); BC_HANDED_IN: this world's partials with the totals of every world
+// handed in (TOT_WEIGHT, TOT_ORGS: cMultiProcessWorld::CalculateUpdateSize,
+// main/cMultiProcessWorld.cc:396-405 -- this world's picks = (int)((local /
+// total) * AVE_TIME_SLICE * N_total)); BC_TOTALS_ONLY: TOT_WEIGHT = root and
+// TOT_ORGS = N out, nothing else written.  The other modes also leave TOT_DIV
+// = the weight total INTEGRATED divides by and TOT_UD = UD.
 // LDS: the whole tree in the workgroup's LDS (P <= TREE_LDS_P: 2 x 4096 doubles
 // + counts = 128 KiB of gfx950's 160).  A larger tree (strips of a world of
 // more than 4096 blocks: the weak-scaling bench at N >= 2, configs[3]) is
@@ -481,7 +483,7 @@ __global__ __launch_bounds__(256) void k_merit_partial(DevWorld W, double* parti
 __device__ __forceinline__ double tree_leaf(const double* part, const int32_t* alive_part, int64_t nb, int64_t nbt,
                                             int mode, int64_t g, long long& a) {
   if (g >= nbt) return 0.0;
-  if (mode == 1) {
+  if (mode == BC_GATHERED) {
     const int64_t k = g / nb, j = g - k * nb;
     a += (long long)part[k * tile_part_stride(nb) + nb + j];
     return part[k * tile_part_stride(nb) + j];
@@ -498,7 +500,7 @@ __global__ __launch_bounds__(1024) void k_block_counts(DevWorld W, const double*
   __shared__ double l_scr[LDS ? 2 * TREE_LDS_P : 1];
   __shared__ long long l_cnt[LDS ? 2 * TREE_LDS_P : 1];
   const int tid = threadIdx.x;
-  const int64_t P = (int64_t)1 << L, nbt = mode == 1 ? nb * ntiles : nb;
+  const int64_t P = (int64_t)1 << L, nbt = mode == BC_GATHERED ? nb * ntiles : nb;
   double* scr = LDS ? l_scr : W.tree_scr;
   long long* cnt = LDS ? l_cnt : reinterpret_cast<long long*>(W.tree_cnt);
   long long a = 0;
@@ -528,50 +530,53 @@ __global__ __launch_bounds__(1024) void k_block_counts(DevWorld W, const double*
     const double root = scr[1];
     const double ave = (double)W.ave_time_slice;
     // the update's UD = AVE_TIME_SLICE x the organisms at its start
-    // (cAvidaDriver's update loop; W.sched[4]), a step's share of that
-    if (sub == 0 && mode != 2) W.sched[4] = (long long)W.ave_time_slice * n;
-    long long nroot = sub_share(W.sched[4], sub, nsub);
-    if (mode == 2) {
-      const double tot = totals[0];
-      nroot = tot > 0.0 ? (long long)__dmul_rn(__dmul_rn(__ddiv_rn(root, tot), ave), totals[1]) : 0;
-      totals[2] = tot;
-      totals[3] = __dmul_rn(ave, totals[1]);
+    // (cAvidaDriver's update loop; SCHED_UD), a step's share of that
+    if (sub == 0 && mode != BC_HANDED_IN) W.sched[SCHED_UD] = (long long)W.ave_time_slice * n;
+    long long nroot = sub_share(W.sched[SCHED_UD], sub, nsub);
+    if (mode == BC_HANDED_IN) {
+      const double tot = totals[TOT_WEIGHT];
+      nroot = tot > 0.0 ? (long long)__dmul_rn(__dmul_rn(__ddiv_rn(root, tot), ave), totals[TOT_ORGS]) : 0;
+      totals[TOT_DIV] = tot;
+      totals[TOT_UD] = __dmul_rn(ave, totals[TOT_ORGS]);
     } else {
-      totals[0] = root;
-      totals[1] = (double)n;
-      totals[2] = root;
-      totals[3] = (double)W.sched[4];
+      totals[TOT_WEIGHT] = root;
+      totals[TOT_ORGS] = (double)n;
+      if (mode != BC_TOTALS_ONLY) {   // (a caller's buffer ends after TOT_HANDED slots)
+        totals[TOT_DIV] = root;
+        totals[TOT_UD] = (double)W.sched[SCHED_UD];
+      }
     }
-    if (mode != 3) {
+    if (mode != BC_TOTALS_ONLY) {
       // the picks the last steps' newborns ran beyond their victims'
       // leftovers come out of an update's first step (oracle take_carry): a
       // strip sums every strip's carry from the gathered partials
-      long long fresh = W.sched[1];
-      if (mode == 1) {
+      long long fresh = W.sched[SCHED_CARRY];
+      if (mode == BC_GATHERED) {
         fresh = 0;
-        for (int k = 0; k < ntiles; k++) fresh += __double_as_longlong(part[k * tile_part_stride(nb) + 2 * nb + 1]);
+        for (int k = 0; k < ntiles; k++)
+          fresh += __double_as_longlong(part[k * tile_part_stride(nb) + tile_tail_off(nb) + TAIL_CARRY]);
       }
-      long long rem = W.sched[2] + fresh;
+      long long rem = W.sched[SCHED_CARRY_REM] + fresh;
       if (sub == 0) {
         const long long take = min(max(rem, -nroot), nroot);
         rem -= take;
         nroot -= take;
       }
-      W.sched[1] = 0;
-      W.sched[2] = rem;
-      count_add(W, CNT_STEPS, 1ull);
+      W.sched[SCHED_CARRY] = 0;
+      W.sched[SCHED_CARRY_REM] = rem;
+      count_add(W, AVGPU_CNT_STEPS, 1ull);
     }
     cnt[1] = nroot;
   }
   __syncthreads();
-  if (mode == 3) return;
+  if (mode == BC_TOTALS_ONLY) return;
   for (int i = tid; i < NSHARD * PACC_STRIDE; i += 1024) W.pacc[i] = 0;   // this step's predictor (interp.hip pred_term)
   // top down, only the nodes over this world's blocks [b0, b0 + nloc) (a
   // node's count depends on its ancestors' alone): a strip of T splits its
   // own subtree and the path to it, not the whole gathered world's tree
   // (chunked: the leaves are chunks, the range in chunks)
   const int sh = chunked ? TREE_C_LOG : 0;
-  const int64_t b0 = mode == 1 ? W.cell0 / 256 : 0;
+  const int64_t b0 = mode == BC_GATHERED ? W.cell0 / 256 : 0;
   const int64_t nloc = (W.n + 255) / 256;
   const int64_t lo = b0 >> sh, hi = (b0 + nloc - 1) >> sh;
   for (int l = 0; l < L; l++) {
@@ -620,7 +625,7 @@ __global__ __launch_bounds__(1024) void k_tree_up(DevWorld W, const double* part
                                                   int64_t nb, int ntiles, int mode) {
   __shared__ double t[2 << TREE_C_LOG];
   __shared__ long long s_cnt[1024];
-  const int64_t nbt = mode == 1 ? nb * ntiles : nb;
+  const int64_t nbt = mode == BC_GATHERED ? nb * ntiles : nb;
   const long long a = chunk_sums(t, s_cnt, part, alive_part, nb, nbt, mode, blockIdx.x);
   if (threadIdx.x == 0) {
     W.tree_scr[blockIdx.x] = t[1];
@@ -637,8 +642,8 @@ __global__ __launch_bounds__(1024) void k_tree_down(DevWorld W, const double* pa
   __shared__ long long c[2 * C];
   __shared__ long long s_cnt[1024];
   const int tid = threadIdx.x;
-  const int64_t nbt = mode == 1 ? nb * ntiles : nb;
-  const int64_t b0 = mode == 1 ? W.cell0 / 256 : 0;
+  const int64_t nbt = mode == BC_GATHERED ? nb * ntiles : nb;
+  const int64_t b0 = mode == BC_GATHERED ? W.cell0 / 256 : 0;
   const int64_t nloc = (W.n + 255) / 256;
   const int64_t k = (b0 >> TREE_C_LOG) + blockIdx.x;
   chunk_sums(t, s_cnt, part, alive_part, nb, nbt, mode, k);
@@ -692,7 +697,7 @@ __global__ __launch_bounds__(1024) void k_allot(DevWorld W, const double* totals
   const int lane = threadIdx.x & 63;
   const int64_t b = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 6);
   const int64_t nb = (W.n + 255) / 256;
-  const double total = totals[2];
+  const double total = totals[TOT_DIV];
   const bool consts = W.slicing == AVGPU_SLICE_CONSTANT || !(total > 0.0);
   const bool prob = !consts && W.slicing != AVGPU_SLICE_INTEGRATED;
   uint32_t ctl[4];
@@ -706,7 +711,7 @@ __global__ __launch_bounds__(1024) void k_allot(DevWorld W, const double* totals
     alive[j] = (ctl[j] & CTL_ALIVE) != 0;
     msz[j] = alive[j] ? W.mem_size[c] : 0;
     const double m = alive[j] ? W.merit[c] : 0.0;
-    if (alive[j] && !merit_ok(m)) count_add(W, CNT_BAD_RECORD, 1ull);   // counted; sched_weight gives it 0
+    if (alive[j] && !merit_ok(m)) count_add(W, AVGPU_CNT_BAD_RECORD, 1ull);   // counted; sched_weight gives it 0
     wt[j] = alive[j] ? sched_weight(m, ctl[j]) : 0.0;
   }
   long long cnt[4] = {0, 0, 0, 0};
@@ -760,7 +765,7 @@ __global__ __launch_bounds__(1024) void k_allot(DevWorld W, const double* totals
       } else if (prob) {
         bud = (int)min(cnt[j], (long long)(BUDGET_PRIM - 1));   // budgets are < 2^30 (device.h)
       } else {
-        double lam = __ddiv_rn(__dmul_rn(totals[3], wt[j]), total);
+        double lam = __ddiv_rn(__dmul_rn(totals[TOT_UD], wt[j]), total);
         if (lam > 1.0e8) lam = 1.0e8;
         const double cr = __dadd_rn(W.credit[c], lam);
         const double fl = floor(cr);
@@ -785,7 +790,7 @@ __global__ __launch_bounds__(1024) void k_allot(DevWorld W, const double* totals
   unsigned long long ns = 0;
 #pragma unroll
   for (int j = 0; j < 4; j++) ns += (unsigned long long)__popcll(__ballot(want[j]));
-  if (lane == 0 && ns) count_add(W, CNT_SLICES, ns);
+  if (lane == 0 && ns) count_add(W, AVGPU_CNT_SLICES, ns);
   int cells[4];
 #pragma unroll
   for (int j = 0; j < 4; j++) cells[j] = (int)(b * 256 + lane + 64 * j);
@@ -1275,12 +1280,12 @@ __global__ void k_place_claim0(DevWorld W, long long* pred_out, long long pred_s
   // the update's last step: its predictor and organisms to the host (mapped
   // memory), which chooses the next update's steps from them
   if (pred_out && blockIdx.x == 0 && threadIdx.x == 0) {
-    pred_out[0] = pacc_sum(W, 0);
-    pred_out[1] = (long long)W.totals[1];
-    pred_out[2] = densest_quarter(W);
+    pred_out[PRED_ACC] = pacc_sum(W, PACC_WEIGHT);
+    pred_out[PRED_ORGS] = (long long)W.totals[TOT_ORGS];
+    pred_out[PRED_DENSEST] = densest_quarter(W);
     // then its sequence number, after them at system scope: the host polls it
     __threadfence_system();
-    __hip_atomic_store(pred_out + 3, pred_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(pred_out + PRED_SEQ, pred_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   QUEUE_LOOP(q) {
     const int64_t r = rec_of(W, q);
@@ -1538,15 +1543,15 @@ __device__ __forceinline__ void newborn_enqueue(const DevWorld& W, int cell, int
 // shipped by k_halo_pack), with the head start 2^16 - t for their first
 // allotment.  The record's fields are loaded before the ownership test
 // (independent loads in flight together instead of a chain behind it).
-// fused 1 (single world): round 3 is resolved here -- a round-3 winner owns
+// fused ACT_WORLD (single world): round 3 is resolved here -- a round-3 winner owns
 // its cell unless the owner from an earlier round is later in time; an
 // earlier round's owner keeps it unless a round-3 winner (necessarily a
-// kill claim: the cell was taken) is not earlier than it.  fused 2 (strip
+// kill claim: the cell was taken) is not earlier than it.  ACT_STRIP (strip
 // tiles): the owners are final (k_tile_round resolved round 3).  Either way
 // each record clears the claims it made (round 3's, which this launch reads,
 // are cleared by k_allot).  A record that does not own its cell was placed
-// and overwritten (CNT_OVERWRITTEN), unless it was cancelled
-// (CNT_CANCELLED: its parent died first) or found no cell (CNT_DROPPED).
+// and overwritten (AVGPU_CNT_OVERWRITTEN), unless it was cancelled
+// (AVGPU_CNT_CANCELLED: its parent died first) or found no cell (AVGPU_CNT_DROPPED).
 #ifndef ACT_PRE
 #define ACT_PRE 8    // 16-B quads of the offspring's genome k_activate loads ahead
 #endif
@@ -1554,8 +1559,8 @@ __global__ __launch_bounds__(64) void k_activate(DevWorld W, int fused, uint32_t
   const int nb = queue_len(W);
   const int64_t ncell = W.n + (W.tiled ? 2 * (int64_t)W.world_x : 0);
   const int lane = threadIdx.x & 63;
-  const double total = W.totals[2];
-  const long long uds = sub_share((long long)W.totals[3], sub, nsub);
+  const double total = W.totals[TOT_DIV];
+  const long long uds = sub_share((long long)W.totals[TOT_UD], sub, nsub);
   unsigned long long born = 0, over = 0, canc = 0, nocell = 0, bad = 0, wasted = 0, nbs = 0;
   long long carry = 0;
   for (int64_t q0 = (int64_t)blockIdx.x * 64; q0 < nb; q0 += (int64_t)gridDim.x * 64) {
@@ -1590,7 +1595,7 @@ __global__ __launch_bounds__(64) void k_activate(DevWorld W, int fused, uint32_t
       if (!ok || tgt < 0 || (int64_t)tgt >= ncell) { bad++; break; }
       const uint32_t t = 0x10000u - b.hs;
       bool won = false;
-      if (fused == 2) {
+      if (fused == ACT_STRIP) {
         won = st >= BS_WON && st < BS_WON + 4 && W.owner[tgt] == (int)i;
       } else if (st == BS_PENDING) {
         won = W.claim_r[3][tgt] == W.b_prio[i] && takes_cell(W, W.owner[tgt], t);
@@ -1621,14 +1626,14 @@ __global__ __launch_bounds__(64) void k_activate(DevWorld W, int fused, uint32_t
     carry += __shfl_xor(carry, off);
   }
   if (threadIdx.x == 0) {
-    if (born) count_add(W, CNT_BIRTHS, born);
-    if (over) count_add(W, CNT_OVERWRITTEN, over);
-    if (canc) count_add(W, CNT_CANCELLED, canc);
-    if (nocell) count_add(W, CNT_DROPPED, nocell);
-    if (bad) count_add(W, CNT_BAD_RECORD, bad);
-    if (wasted) count_add(W, CNT_WASTED, wasted);
-    if (nbs) count_add(W, CNT_SLICES, nbs);
-    if (carry) atomicAdd(reinterpret_cast<unsigned long long*>(W.sched + 1), (unsigned long long)carry);
+    if (born) count_add(W, AVGPU_CNT_BIRTHS, born);
+    if (over) count_add(W, AVGPU_CNT_OVERWRITTEN, over);
+    if (canc) count_add(W, AVGPU_CNT_CANCELLED, canc);
+    if (nocell) count_add(W, AVGPU_CNT_DROPPED, nocell);
+    if (bad) count_add(W, AVGPU_CNT_BAD_RECORD, bad);
+    if (wasted) count_add(W, AVGPU_CNT_WASTED, wasted);
+    if (nbs) count_add(W, AVGPU_CNT_SLICES, nbs);
+    if (carry) atomicAdd(reinterpret_cast<unsigned long long*>(W.sched + SCHED_CARRY), (unsigned long long)carry);
   }
 }
 
@@ -1695,8 +1700,8 @@ __global__ __launch_bounds__(64) void k_halo_pack(DevWorld W) {
     }
   }
   if (lane == 0) {
-    if (sent) count_add(W, CNT_HALO_SENT, sent);
-    if (lost) { count_add(W, CNT_HALO_LOST, lost); count_add(W, CNT_DROPPED, lost); }
+    if (sent) count_add(W, AVGPU_CNT_HALO_SENT, sent);
+    if (lost) { count_add(W, AVGPU_CNT_HALO_LOST, lost); count_add(W, AVGPU_CNT_DROPPED, lost); }
   }
 }
 
@@ -1704,8 +1709,8 @@ __global__ __launch_bounds__(64) void k_halo_pack(DevWorld W) {
 // it was that cell's last winner (owner == REMOTE_OWNER(its round)).
 __global__ __launch_bounds__(64) void k_activate_remote(DevWorld W, uint32_t key, int sub, int nsub) {
   const int lane = threadIdx.x;
-  const double total = W.totals[2];
-  const long long uds = sub_share((long long)W.totals[3], sub, nsub);
+  const double total = W.totals[TOT_DIV];
+  const long long uds = sub_share((long long)W.totals[TOT_UD], sub, nsub);
   long long carry = 0;
   unsigned long long wasted = 0, nbs = 0;
   const int X = W.world_x;
@@ -1722,10 +1727,10 @@ __global__ __launch_bounds__(64) void k_activate_remote(DevWorld W, uint32_t key
     const HaloRec r = recs[q];
     if (r.len < 0) continue;                  // lost at the sender (counted there)
     // fields used as indices / lengths are checked: a record the exchange
-    // delivered damaged is counted (CNT_BAD_RECORD), never followed
+    // delivered damaged is counted (AVGPU_CNT_BAD_RECORD), never followed
     if (r.col < 0 || r.col >= X || r.len > AVGPU_MAX_GENOME || r.off < 0 || (r.off & 3) ||
         (int64_t)r.off + r.len > W.r_arena || r.round < 0 || r.round > 3) {
-      if (lane == 0) count_add(W, CNT_BAD_RECORD, 1ull);
+      if (lane == 0) count_add(W, AVGPU_CNT_BAD_RECORD, 1ull);
       continue;
     }
     const int64_t c = edge_cell(W, d, r.col);
@@ -1748,20 +1753,16 @@ __global__ __launch_bounds__(64) void k_activate_remote(DevWorld W, uint32_t key
     }
   }
   if (lane == 0) {
-    if (born) count_add(W, CNT_BIRTHS, born);
-    if (lost) count_add(W, CNT_OVERWRITTEN, lost);
-    if (wasted) count_add(W, CNT_WASTED, wasted);
-    if (nbs) count_add(W, CNT_SLICES, nbs);
-    if (carry) atomicAdd(reinterpret_cast<unsigned long long*>(W.sched + 1), (unsigned long long)carry);
+    if (born) count_add(W, AVGPU_CNT_BIRTHS, born);
+    if (lost) count_add(W, AVGPU_CNT_OVERWRITTEN, lost);
+    if (wasted) count_add(W, AVGPU_CNT_WASTED, wasted);
+    if (nbs) count_add(W, AVGPU_CNT_SLICES, nbs);
+    if (carry) atomicAdd(reinterpret_cast<unsigned long long*>(W.sched + SCHED_CARRY), (unsigned long long)carry);
   }
 }
 
 // ---- statistics: per-block partials, then one block ----
-// partial slots: 0 orgs 1 merit 2 fitness 3 gestation 4 genome length 5 max fitness
-// 6 generation 7 memory size 8..16 task organisms
-#define NPART 24
-#define NUSED (8 + AVGPU_NUM_LOGIC_TASKS)
-#define NSTAT 45
+// (the slots: device.h ST_*; the first NUSED of them have a partial row)
 __device__ __forceinline__ double wave_sum(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
@@ -1788,7 +1789,7 @@ __global__ __launch_bounds__(256) void k_stats_partial(DevWorld W, double* part)
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   double merit = 0.0, fit = 0.0;
-  int iv[5] = {0, 0, 0, 0, 0};                 // slots 0 3 4 6 7
+  int iv[5] = {0, 0, 0, 0, 0};                 // ST_ORGS, _GESTATION, _GENOME_LEN, _GENERATION, _MEM_SIZE
   unsigned long long tasks = 0;
   if (c < W.n && (W.ctl[c] & CTL_ALIVE)) {
     merit = W.merit[c];
@@ -1808,10 +1809,11 @@ __global__ __launch_bounds__(256) void k_stats_partial(DevWorld W, double* part)
   for (int k = 0; k < 5; k++) ri[k] = wave_sum_i(iv[k]);
   const unsigned long long rt = wave_sum_u64(tasks);
   if (lane == 0) {
-    s[wv][0] = (double)ri[0]; s[wv][1] = rm; s[wv][2] = rf; s[wv][3] = (double)ri[1];
-    s[wv][4] = (double)ri[2]; s[wv][5] = rx; s[wv][6] = (double)ri[3]; s[wv][7] = (double)ri[4];
+    s[wv][ST_ORGS] = (double)ri[0]; s[wv][ST_MERIT] = rm; s[wv][ST_FITNESS] = rf;
+    s[wv][ST_GESTATION] = (double)ri[1]; s[wv][ST_GENOME_LEN] = (double)ri[2]; s[wv][ST_MAX_FITNESS] = rx;
+    s[wv][ST_GENERATION] = (double)ri[3]; s[wv][ST_MEM_SIZE] = (double)ri[4];
 #pragma unroll
-    for (int t = 0; t < AVGPU_NUM_LOGIC_TASKS; t++) s[wv][8 + t] = (double)((rt >> (7 * t)) & 127ull);
+    for (int t = 0; t < AVGPU_NUM_LOGIC_TASKS; t++) s[wv][ST_TASK0 + t] = (double)((rt >> (7 * t)) & 127ull);
   }
   __syncthreads();
   // only the NUSED slots carry data (the rest of the NPART rows are never
@@ -1819,13 +1821,12 @@ __global__ __launch_bounds__(256) void k_stats_partial(DevWorld W, double* part)
   if (threadIdx.x < NUSED) {
     const int k = threadIdx.x;
     double r = s[0][k];
-    for (int q = 1; q < 4; q++) r = (k == 5) ? fmax(r, s[q][k]) : r + s[q][k];
+    for (int q = 1; q < 4; q++) r = (k == ST_MAX_FITNESS) ? fmax(r, s[q][k]) : r + s[q][k];
     part[(int64_t)k * gridDim.x + blockIdx.x] = r;
   }
 }
 
-// out: [0..23] partial sums, 24 insts 25 deaths 26 divides 27 births 28 dropped
-// 29 spills 30 cumulative insts 31 cumulative births 32 slices 33 lane steps.
+// out: the statistics vector's NSTAT slots (device.h ST_*).
 // Block k < NPART reduces partial row k (256 lanes, fixed order: lane t sums
 // entries t, t+256, ..., then a pairwise tree); block NPART sums the counter
 // shards.
@@ -1841,7 +1842,7 @@ __global__ __launch_bounds__(256) void k_stats_final(DevWorld W, const double* p
     return;
   }
   if (k < NPART) {
-    const bool mx = k == 5;
+    const bool mx = k == ST_MAX_FITNESS;
     double acc = 0.0;
     for (int64_t b = tid; b < nb; b += 256) {
       const double o = part[(int64_t)k * nb + b];
@@ -1876,24 +1877,24 @@ __global__ __launch_bounds__(256) void k_stats_final(DevWorld W, const double* p
   }
   __syncthreads();
   if (tid == 0) {
-    out[24] = (double)cs[0][CNT_INSTS];
-    out[25] = (double)cs[0][CNT_DEATHS];
-    out[26] = (double)cs[0][CNT_DIVIDES];
-    out[27] = (double)cs[0][CNT_BIRTHS];
-    out[28] = (double)cs[0][CNT_DROPPED];
-    out[29] = (double)cs[0][CNT_SPILLS];
-    out[30] = (double)W.counters[CNT_CUM_INSTS];
-    out[31] = (double)W.counters[CNT_CUM_BIRTHS];
-    out[32] = (double)cs[0][CNT_SLICES];
-    out[33] = (double)cs[0][CNT_LANESTEPS];
-    out[34] = (double)cs[0][CNT_OVERWRITTEN];
-    out[35] = (double)cs[0][CNT_CANCELLED];
-    out[36] = (double)cs[0][CNT_WASTED];
-    out[37] = __longlong_as_double(pacc_sum(W, 0));         // the predictor (bits)
-    out[38] = __longlong_as_double(W.sched[1] + W.sched[2]); // the pick carry (bits)
-    out[39] = W.totals[1];                                  // the organisms it is relative to
-    out[40] = __longlong_as_double(densest_quarter(W));
-    for (int q = 0; q < 4; q++) out[41 + q] = __longlong_as_double(quarter_count(W, q));   // (bits)
+    out[ST_INSTS] = (double)cs[0][AVGPU_CNT_INSTS];
+    out[ST_DEATHS] = (double)cs[0][AVGPU_CNT_DEATHS];
+    out[ST_DIVIDES] = (double)cs[0][AVGPU_CNT_DIVIDES];
+    out[ST_BIRTHS] = (double)cs[0][AVGPU_CNT_BIRTHS];
+    out[ST_DROPPED] = (double)cs[0][AVGPU_CNT_DROPPED];
+    out[ST_SPILLS] = (double)cs[0][AVGPU_CNT_SPILLS];
+    out[ST_CUM_INSTS] = (double)W.counters[CNT_CUM_INSTS];
+    out[ST_CUM_BIRTHS] = (double)W.counters[CNT_CUM_BIRTHS];
+    out[ST_SLICES] = (double)cs[0][AVGPU_CNT_SLICES];
+    out[ST_LANESTEPS] = (double)cs[0][AVGPU_CNT_LANESTEPS];
+    out[ST_OVERWRITTEN] = (double)cs[0][AVGPU_CNT_OVERWRITTEN];
+    out[ST_CANCELLED] = (double)cs[0][AVGPU_CNT_CANCELLED];
+    out[ST_WASTED] = (double)cs[0][AVGPU_CNT_WASTED];
+    out[ST_PRED] = __longlong_as_double(pacc_sum(W, PACC_WEIGHT));
+    out[ST_CARRY] = __longlong_as_double(W.sched[SCHED_CARRY] + W.sched[SCHED_CARRY_REM]);
+    out[ST_PRED_ORGS] = W.totals[TOT_ORGS];
+    out[ST_PRED_DENSEST] = __longlong_as_double(densest_quarter(W));
+    for (int q = 0; q < 4; q++) out[ST_QUARTER0 + q] = __longlong_as_double(quarter_count(W, q));
   }
 }
 
@@ -1932,7 +1933,7 @@ void launch_set_states(const DevWorld& W, hipStream_t s, int64_t first, int64_t 
 
 void launch_classify_uniform(const DevWorld& W, hipStream_t s, int64_t first, int64_t count,
                              const int32_t* budget, int32_t uniform) {
-  hipMemsetAsync(W.class_count, 0, sizeof(int32_t) * 8, s);
+  hipMemsetAsync(W.class_count, 0, sizeof(int32_t) * CLASS_COUNT_WORDS, s);
   hipLaunchKernelGGL(k_classify_uniform, dim3(nblk(count, 256)), dim3(256), 0, s, W, first, count,
                      budget, uniform);
 }
@@ -1952,8 +1953,8 @@ static void launch_block_counts(const DevWorld& W, hipStream_t s, const double* 
   // (2^23 blocks at most, so K <= 2^11)
   hipLaunchKernelGGL(k_block_counts<true>, dim3(1), dim3(1024), 0, s, W, part, alive, nb, ntiles, Lt, totals,
                      update, mode, 1, sub, nsub);
-  if (mode == 3) return;
-  const int64_t b0 = mode == 1 ? W.cell0 / 256 : 0, nloc = (W.n + 255) / 256;
+  if (mode == BC_TOTALS_ONLY) return;
+  const int64_t b0 = mode == BC_GATHERED ? W.cell0 / 256 : 0, nloc = (W.n + 255) / 256;
   const int64_t nk = ((b0 + nloc - 1) >> TREE_C_LOG) - (b0 >> TREE_C_LOG) + 1;
   hipLaunchKernelGGL(k_tree_down, dim3((unsigned)nk), dim3(1024), 0, s, W, part, alive, nb, ntiles, mode, K, update);
 }
@@ -1964,14 +1965,15 @@ static int tree_levels(int64_t nbt) {
   return L;
 }
 
-// totals: [0] total weight, [1] organisms (mode 3 of k_block_counts).
+// totals: TOT_WEIGHT and TOT_ORGS, a buffer of TOT_HANDED doubles
+// (k_block_counts BC_TOTALS_ONLY).
 // scratch: (n+255)/256 doubles + as many int32 partials
 void launch_merit_total(const DevWorld& W, hipStream_t s, double* totals, double* scratch) {
   const int64_t nb = (W.n + 255) / 256;
   int32_t* alive_partial = reinterpret_cast<int32_t*>(scratch + nb);
   hipLaunchKernelGGL(k_merit_partial, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, W, scratch, alive_partial,
-                     (double*)nullptr, 0);
-  launch_block_counts(W, s, scratch, alive_partial, nb, 1, tree_levels(nb), totals, 0u, 3);
+                     (double*)nullptr, RESET_NONE);
+  launch_block_counts(W, s, scratch, alive_partial, nb, 1, tree_levels(nb), totals, 0u, BC_TOTALS_ONLY);
 }
 
 // the update's counters, birth-queue and class-list lengths, zeroed by one
@@ -1990,27 +1992,28 @@ static void launch_allot(const DevWorld& W, hipStream_t s, const double* totals,
 
 // single world: block partials (k_merit_partial also zeroes the update's
 // counters), the scheduler's top tree, the allotment, the class-0 order.
-// The picks come from the world's own totals (k_block_counts mode 0) or from
-// totals handed in in totals[0..1] (mode 2; device.h)
+// The picks come from the world's own totals (k_block_counts BC_OWN) or from
+// totals handed in (BC_HANDED_IN; device.h)
 void launch_world_begin(const DevWorld& W, hipStream_t s, double* totals, double* scratch, uint32_t update,
                         int sub, int nsub, bool own_totals) {
   const int64_t nb = (W.n + 255) / 256;
   int32_t* alive_partial = reinterpret_cast<int32_t*>(scratch + nb);
   if (sub == 0) launch_resources_begin(W, s);   // ProcessPreUpdate + the update's first DoUpdates
   hipLaunchKernelGGL(k_merit_partial, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, s, W, scratch, alive_partial,
-                     (double*)nullptr, sub == 0 ? 1 : 2);
-  launch_block_counts(W, s, scratch, alive_partial, nb, 1, tree_levels(nb), totals, update, own_totals ? 0 : 2, sub,
-                      nsub);
+                     (double*)nullptr, sub == 0 ? RESET_COUNTS : RESET_QUEUES);
+  launch_block_counts(W, s, scratch, alive_partial, nb, 1, tree_levels(nb), totals, update,
+                      own_totals ? BC_OWN : BC_HANDED_IN, sub, nsub);
   launch_allot(W, s, totals, update, sub == 0 ? 1 : 0);
 }
 
-// a strip tile: the top tree over every strip's gathered partials (mode 1),
+// a strip tile: the top tree over every strip's gathered partials (BC_GATHERED),
 // then the allotment (its partials' launch cleared the counters)
 void launch_tile_pre(const DevWorld& W, hipStream_t s, const double* gathered, int ntiles, double* totals,
                      uint32_t update, int sub, int nsub) {
   const int64_t nb = (W.n + 255) / 256;
   if (sub == 0) launch_resources_begin(W, s);
-  launch_block_counts(W, s, gathered, nullptr, nb, ntiles, tree_levels(nb * ntiles), totals, update, 1, sub, nsub);
+  launch_block_counts(W, s, gathered, nullptr, nb, ntiles, tree_levels(nb * ntiles), totals, update, BC_GATHERED, sub,
+                      nsub);
   launch_allot(W, s, totals, update, sub == 0 ? 1 : 0);
 }
 
@@ -2054,9 +2057,9 @@ void launch_reset_counts(const DevWorld& W, hipStream_t s) {
   hipLaunchKernelGGL(k_reset_counts, dim3(1), dim3(256), 0, s, W);
 }
 
-// Placement rounds alternate between the claim arrays claim / claim2 (round k
-// claims into array k & 1 after zeroing its records' round k-1 claims; the
-// last round's are zeroed by k_activate): no clearing launch per round.
+// Placement round k claims into its own array claim_r[k] (device.h): no
+// clearing launch per round.  Each record clears the claims it made when it
+// is activated; round 3's, which k_activate reads, are cleared by k_allot.
 void launch_world_post(const DevWorld& W, hipStream_t s, uint32_t key, int sub, int nsub, long long* pred_out,
                        long long pred_seq) {
   // the occupancy was initialised by k_allot; the divide mutations
@@ -2088,7 +2091,7 @@ void launch_world_post(const DevWorld& W, hipStream_t s, uint32_t key, int sub, 
     if (soup) soup_cells(m);
     hipLaunchKernelGGL(k_place_round, dim3(bb), dim3(256), 0, s, W, m);
   }
-  hipLaunchKernelGGL(k_activate, dim3(lane_grid(W)), dim3(64), 0, s, W, 1, key, sub, nsub);
+  hipLaunchKernelGGL(k_activate, dim3(lane_grid(W)), dim3(64), 0, s, W, ACT_WORLD, key, sub, nsub);
 }
 
 // after the newborn pass (interp.hip): the step's global consumption settled,
@@ -2115,25 +2118,25 @@ void launch_tile_after_interpret(const DevWorld& W, hipStream_t s) {
   hipLaunchKernelGGL(k_tile_prep, dim3(mb + fb + hb), dim3(256), 0, s, W, mb, fb);
 }
 
-// phase 0: round 0's picks and kill times, or (round 1..3) k_tile_round:
-//          resolve round - 1, pick round
-// phase 3: (round 0) the cancellations and round 0's claims (k_tile_claim0)
-// phase 1: (round 3) the last resolve, then the ghost-row winners packed into
-//          the record buffers
-// phase 2: (round 3) this tile's own winners activated -- while the records
-//          travel; avgpu_tile_finish then activates the received ones
+// TP_ROUND:    round 0's picks and kill times, or (round 1..3) k_tile_round:
+//              resolve round - 1, pick round
+// TP_CLAIM0:   (round 0) the cancellations and round 0's claims (k_tile_claim0)
+// TP_PACK:     (round 3) the last resolve, then the ghost-row winners packed
+//              into the record buffers
+// TP_ACTIVATE: (round 3) this tile's own winners activated -- while the records
+//              travel; avgpu_tile_finish then activates the received ones
 void launch_tile_place(const DevWorld& W, hipStream_t s, int round, int phase, uint32_t key, int sub, int nsub) {
   const unsigned bb = place_grid(W);
   const unsigned hb = nblk(2 * (int64_t)W.world_x, 256);
-  if (phase == 0) {
+  if (phase == TP_ROUND) {
     hipLaunchKernelGGL(k_tile_round, dim3(bb + hb), dim3(256), 0, s, W, round, (int)bb);
-  } else if (phase == 3) {
+  } else if (phase == TP_CLAIM0) {
     hipLaunchKernelGGL(k_tile_claim0, dim3(bb), dim3(256), 0, s, W);
-  } else if (phase == 1) {
+  } else if (phase == TP_PACK) {
     hipLaunchKernelGGL(k_tile_round, dim3(bb + hb), dim3(256), 0, s, W, 4, (int)bb);
     hipLaunchKernelGGL(k_halo_pack, dim3(lane_grid(W)), dim3(64), 0, s, W);
   } else {
-    hipLaunchKernelGGL(k_activate, dim3(lane_grid(W)), dim3(64), 0, s, W, 2, key, sub, nsub);
+    hipLaunchKernelGGL(k_activate, dim3(lane_grid(W)), dim3(64), 0, s, W, ACT_STRIP, key, sub, nsub);
   }
 }
 

@@ -665,9 +665,13 @@ int avgpu_test_genomes(avgpu_world* w, int n, const uint8_t* genomes, const int3
 /* ---- statistics / multi-GPU plumbing ------------------------------------ */
 /* the last update's statistics (reduced here if that update ran with out == NULL) */
 int avgpu_get_stats(avgpu_world* w, avgpu_update_stats* out);
-/* device pointer of the 32-double reduction vector of the last update
- * (N, sum merit, executed, births, ...) for an external all-reduce
- * (RCCL, cMultiProcessWorld.cc:375-405); avgpu_set_global_merit feeds the
+/* device pointer of the 45-double statistics vector of the last update
+ * (reduced here if that update ran with out == NULL) for an external
+ * all-reduce (RCCL, cMultiProcessWorld.cc:375-405): organisms, the sums of
+ * merit, fitness, gestation time and genome length, max fitness, the sums of
+ * generation and memory size, the nine task-organism counts, then from slot
+ * 24 the update's counters and the scheduler's state, the latter as int64
+ * bits (the slot list: csrc/device.h ST_*).  avgpu_set_global_totals feeds
  * reduced totals back before the next allotment. */
 int avgpu_stats_vector(avgpu_world* w, void** dev_ptr);
 /* total_merit: the SUM OF SCHEDULER WEIGHTS over every world (as
@@ -794,7 +798,15 @@ enum avgpu_counter {
   AVGPU_CNT_LANESTEPS = 7,  /* 64 x longest lane per wave (lane efficiency = INSTS / this) */
   AVGPU_CNT_C0_SLICES = 8,  /* slices run by the class-0 launch (its windows, the list-class blocks inside it, its in-wave spill continuations) */
   AVGPU_CNT_C0_SITES = 9,   /* tape sites that launch staged in plus wrote back */
-  /* 10..17: per-phase clocks of diagnostic (AVGPU_PHASE_CLOCKS) builds */
+  /* 10..17: diagnostic (AVGPU_PHASE_CLOCKS) builds only, per interpreter wave */
+  AVGPU_CNT_CLK_STAGE = 10, /* cycles staging in, */
+  AVGPU_CNT_CLK_LOOP = 11,  /* in the loop, */
+  AVGPU_CNT_CLK_WB = 12,    /* writing back */
+  AVGPU_CNT_ITERS = 13,     /* loop iterations of the wave */
+  AVGPU_CNT_IT_FAST = 14,   /* iterations in which some lane took the branch-free block, */
+  AVGPU_CNT_IT_COPY = 15,   /* the h-copy block, */
+  AVGPU_CNT_IT_SLOW = 16,   /* the switch */
+  AVGPU_CNT_WAVES = 17,
   AVGPU_CNT_HALO_SENT = 18, /* offspring shipped to a neighbouring tile */
   AVGPU_CNT_HALO_LOST = 19, /* offspring dropped because the halo arena was full */
   AVGPU_CNT_REC_EXHAUSTED = 20, /* RECORDED draws past the end of the stream */
@@ -808,7 +820,13 @@ enum avgpu_counter {
                                (the reference's parent died first: never placed) */
   AVGPU_CNT_BAD_RECORD = 26, /* record or cell fields out of range where used as an index or length
                                 (guarded, counted, never used; must be 0) */
-  AVGPU_NUM_COUNTERS = 48   /* 32..47: AVGPU_PHASE_CLOCKS diagnostic builds */
+  AVGPU_CNT_WASTED = 27,    /* instructions replaced organisms ran after their newborns' birth times */
+  AVGPU_CNT_STEPS = 28,     /* batch steps (one per step of an update) */
+  /* 32..47: AVGPU_PHASE_CLOCKS diagnostic builds */
+  AVGPU_CNT_CB0 = 32,       /* .. 37: loop cycles by block (decode, fast, copy, switch, wave phase, advance) */
+  AVGPU_CNT_CASE0 = 38,     /* .. 47: slow-switch cycles by case (pop, push, IO, h-alloc, h-divide,
+                               h-search / if-label, ...) */
+  AVGPU_NUM_COUNTERS = 48
 };
 int avgpu_counters(avgpu_world* w, int cumulative, int64_t* out, int n);
 

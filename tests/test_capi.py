@@ -45,6 +45,28 @@ def test_struct_layouts(tmp_path):
     assert got == exp
 
 
+def test_counter_slots_match_the_header(tmp_path):
+    """enum avgpu_counter is the one list of counter slots in C; capi.py
+    restates it for ctypes clients, which cannot include the header: every
+    enumerator, as a C compiler evaluates it, equals capi's constant of the
+    same name, and capi has no slot the header lacks."""
+    body = re.search(r"enum avgpu_counter \{(.*?)\};", open(HEADER).read(), re.S).group(1)
+    names = re.findall(r"\b(AVGPU_CNT_[A-Z0-9_]+)\s*=", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+    assert "AVGPU_CNT_WASTED" in names and "AVGPU_CNT_STEPS" in names
+    src = tmp_path / "cnt.c"
+    src.write_text('#include "avida_gpu.h"\n#include <stdio.h>\nint main(){\n' +
+                   "".join(f'printf("{n} %d\\n", (int){n});\n' for n in names + ["AVGPU_NUM_COUNTERS"]) +
+                   "return 0;}\n")
+    exe = tmp_path / "cnt"
+    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    got = {k: int(v) for k, v in (ln.split() for ln in subprocess.check_output([str(exe)], text=True).splitlines())}
+    assert got.pop("AVGPU_NUM_COUNTERS") == capi.NUM_COUNTERS
+    mirror = {"AVGPU_" + k: v for k, v in vars(capi).items() if k.startswith("CNT_")}
+    assert got == mirror
+    assert got["AVGPU_CNT_WASTED"] == 27 and got["AVGPU_CNT_STEPS"] == 28
+    assert len(set(got.values())) == len(got) and max(got.values()) < capi.NUM_COUNTERS
+
+
 def test_cfg_defaults_match_avida_cfg(golden):
     from avida_amd import files
     lib = C.CDLL(capi.LIB_PATH)

@@ -215,6 +215,98 @@ def test_handed_in_totals_equal_oracle(golden):
     assert gpu.counters(cumulative=1)[capi.CNT_BAD_RECORD] == 0
 
 
+STATS_INT_FIELDS = ("update", "num_organisms", "insts_executed", "births", "births_dropped", "deaths", "divides",
+                    "cum_insts_executed", "cum_births", "slices", "births_overwritten", "births_cancelled", "seed",
+                    "sched_pred", "sched_pred_n", "sub_steps", "sched_carry", "insts_wasted", "sched_pred_cnt")
+STATS_SUM_FIELDS = ("sum_merit", "sum_fitness", "sum_gestation", "sum_genome_length", "sum_mem_size",
+                    "ave_generation")
+
+
+def test_every_stats_field_equals_oracle(golden):
+    """Every field of avgpu_update_stats of a batch-world update, GPU against
+    oracle: the statistics vector's slots (device.h ST_*) one by one, so that
+    a swapped or shifted slot fails here and not only where it bends a later
+    trajectory.  handed_in_world on its own totals, adaptive batch steps
+    (sub_updates = 0): 20 updates, avgpu_set_clock on both backends with their
+    own last statistics (every slot it writes: the running sums, the pick
+    carry, the predictor's shard words and organisms), 20 more.  Integer
+    fields and max_fitness equal; the double sums and ave_generation within
+    1e-12 relative (sums added in different orders: test_serial_gpu's bound);
+    lane_steps, which the oracle does not produce, positive.  On the oracle's
+    own values: every compared field but births_dropped non-zero in some
+    update, an update of more than one batch step, a pick carry of each
+    sign."""
+    import ctypes as C
+    iset, env, cfg, genomes, merits = handed_in_world(golden)
+    cfg.sub_updates = 0
+    n = len(genomes)
+    orc = ol.Backend("oracle", cfg, iset, env, ncells=n)
+    gpu = ol.Backend("gpu", cfg, iset, env, ncells=n)
+    for b in (orc, gpu):
+        b.set_orgs(0, genomes, merits, deterministic=False)
+    ntask = 9                              # the logic-9 tasks
+    seen = {f: False for f in STATS_INT_FIELDS + STATS_SUM_FIELDS + ("max_fitness",)}
+    seen.update({("task_orgs", t): False for t in range(ntask)})
+    seen.update({("sched_pred_bins", q): False for q in range(4)})
+    steps, carries = [], []
+    for upd in range(40):
+        if upd == 20:
+            for b, st in ((orc, so), (gpu, sg)):
+                b._call("set_clock", b.h, C.byref(st))
+        so = orc.run_update()
+        sg = gpu.run_update()
+        for f in STATS_INT_FIELDS:
+            assert getattr(so, f) == getattr(sg, f), (upd, f, getattr(so, f), getattr(sg, f))
+        assert list(so.task_orgs) == list(sg.task_orgs), (upd, list(so.task_orgs), list(sg.task_orgs))
+        assert list(so.sched_pred_bins) == list(sg.sched_pred_bins), (upd, list(so.sched_pred_bins),
+                                                                      list(sg.sched_pred_bins))
+        assert so.max_fitness == sg.max_fitness, (upd, so.max_fitness, sg.max_fitness)
+        for f in STATS_SUM_FIELDS:
+            a, b = getattr(so, f), getattr(sg, f)
+            assert abs(a - b) <= 1e-12 * abs(a), (upd, f, a, b)
+        assert sg.lane_steps > 0, upd
+        for f in STATS_INT_FIELDS + STATS_SUM_FIELDS + ("max_fitness",):
+            seen[f] |= getattr(so, f) != 0
+        for t in range(ntask):
+            seen[("task_orgs", t)] |= so.task_orgs[t] != 0
+        for q in range(4):
+            seen[("sched_pred_bins", q)] |= so.sched_pred_bins[q] != 0
+        steps.append(so.sub_steps)
+        carries.append(so.sched_carry)
+    never = [f for f, s in seen.items() if not s and f != "births_dropped"]
+    assert not never, f"always zero in the oracle: {never}"
+    assert max(steps) > 1, steps
+    assert min(carries) < 0 < max(carries), carries
+
+
+def test_update_totals_stays_within_its_buffer(golden):
+    """avgpu_update_totals writes the two doubles its header documents --
+    the sum of scheduler weights and the living organisms -- and nothing past
+    them: of an 8-double device buffer of sentinels, doubles 2..7 keep their
+    bits.  handed_in_world as loaded: no organism is a fresh newborn, so its
+    weight is its merit."""
+    import ctypes as C
+    import numpy as np
+    import torch
+    iset, env, cfg, genomes, merits = handed_in_world(golden)
+    n = len(genomes)
+    gpu = ol.Backend("gpu", cfg, iset, env, ncells=n)
+    gpu.set_orgs(0, genomes, merits, deterministic=False)
+    sentinel = 0x7FF4C0DE5E1271E1          # a NaN no sum produces
+    buf = torch.full((8,), sentinel, dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    gpu._call("update_totals", gpu.h, C.c_void_p(buf.data_ptr()))
+    gpu.lib.avgpu_sync(gpu.h)
+    got = buf.cpu().numpy()
+    assert got[2:].tolist() == [sentinel] * 6, [hex(v) for v in got.tolist()]
+    weight, orgs = got[:2].view(np.float64).tolist()
+    s, _ = handed_in_view(gpu, n)
+    alive = s["alive"] != 0
+    assert orgs == int(alive.sum()) > 0, (orgs, int(alive.sum()))
+    want = float(s["merit"][alive].sum())
+    assert want > 0 and abs(weight - want) <= 1e-12 * want, (weight, want)
+
+
 def test_lazy_statistics_equal_eager(golden):
     """An update run with out == NULL skips the statistics reduction (the bench
     regime); the counts still reach the running sums (folded in by the next
