@@ -217,6 +217,18 @@ def get_genotypes(lib, handle):
         cap = lib._genotype_cap = int(totals.num_genotypes) + int(totals.num_genotypes) // 4 + 16
 
 
+# avgpu_landscape (include/avida_gpu.h): one row per base genome
+MAX_INST = 64
+LANDSCAPE_DTYPE = np.dtype([("total_count", "<i8"), ("dead_count", "<i8"), ("neg_count", "<i8"),
+                            ("neut_count", "<i8"), ("pos_count", "<i8"), ("gestations", "<i8", (3,)),
+                            ("peak_rank", "<i8"), ("base_fitness", "<f8"), ("base_merit", "<f8"),
+                            ("peak_fitness", "<f8"), ("total_fitness", "<f8"), ("total_sqr_fitness", "<f8"),
+                            ("pos_size", "<f8"), ("neg_size", "<f8"), ("total_entropy", "<f8"),
+                            ("complexity", "<f8"), ("base_gestation", "<i4"), ("distance", "<i4"),
+                            ("genome_length", "<i4"), ("num_insts", "<i4")])
+assert LANDSCAPE_DTYPE.itemsize == 160
+
+
 # C-ABI symbols declared in include/avida_gpu.h (checked by tests/test_capi.py)
 EXPORTED = [
     "avgpu_last_error", "avgpu_cfg_defaults", "avgpu_check_cfg", "avgpu_create", "avgpu_destroy", "avgpu_sync",
@@ -232,6 +244,7 @@ EXPORTED = [
     "avgpu_state_digests", "avgpu_set_rng_mode", "avgpu_run_serial_updates", "avgpu_set_serial_streams",
     "avgpu_get_serial_state", "avgpu_set_serial_state", "avgpu_set_timing",
     "avgpu_get_genotypes", "avgpu_last_genotypes_ms",
+    "avgpu_landscapes", "avgpu_set_landscape_chunk", "avgpu_last_landscape_ms",
 ]
 
 
@@ -482,6 +495,15 @@ def load_product(path=None):
     lib.avgpu_get_genotypes.restype = C.c_int
     lib.avgpu_get_genotypes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GENOTYPE_TOTALS)]
     lib.avgpu_last_genotypes_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    # mutational landscapes: the product only (the oracle runs avida_amd.landscape.spec)
+    lib.avgpu_landscapes.restype = C.c_int
+    lib.avgpu_landscapes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int,
+                                     C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    lib.avgpu_set_landscape_chunk.restype = C.c_int
+    lib.avgpu_set_landscape_chunk.argtypes = [C.c_void_p, C.c_int64]
+    lib.avgpu_last_landscape_ms.restype = C.c_int
+    lib.avgpu_last_landscape_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                            C.POINTER(C.c_int64)]
     if path is None:
         _lib = lib
     return lib

@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "device.h"
@@ -120,6 +121,15 @@ struct avgpu_world {
   hipEvent_t ev_gt[4] = {};
   double gt_ms = 0.0;
   int64_t gt_bytes = 0;
+  // mutational landscapes (avgpu_landscapes): the scratch test world of
+  // land_chunk cells the mutants run through and the per-chunk scratch (in its
+  // allocs), created by the first call, re-created when land_chunk changes
+  avgpu_world* land = nullptr;
+  LandScratch land_s = {};
+  int64_t land_chunk = 65536;
+  hipEvent_t ev_land[2] = {};
+  double land_ms = 0.0;
+  int64_t land_mutants = 0, land_runs = 0;
 
   template <typename T>
   int alloc(T** p, size_t count) {
@@ -703,6 +713,8 @@ int avgpu_destroy(avgpu_world* w) {
   if (!w) return 0;
   if (w->stream) hipStreamSynchronize(w->stream);
   if (w->own_stream) hipStreamSynchronize(w->own_stream);
+  if (w->land) avgpu_destroy(w->land);
+  for (hipEvent_t e : w->ev_land) if (e) hipEventDestroy(e);
   for (void* p : w->allocs) hipFree(p);
   if (w->rec_buf) hipFree(w->rec_buf);
   for (double* p : w->srec_buf) if (p) hipFree(p);
@@ -1626,6 +1638,219 @@ int avgpu_test_genomes(avgpu_world* w, int n, const uint8_t* genomes, const int3
     off += lens[i];
   }
   avgpu_destroy(t);
+  return 0;
+}
+
+// ---- mutational landscapes (landscape.hip) ----
+// the scratch test world and the per-chunk scratch, for the current land_chunk
+static int land_alloc(avgpu_world* w) {
+  if (w->land && w->land_s.chunk == w->land_chunk) return 0;
+  if (w->land) {
+    avgpu_destroy(w->land);
+    w->land = nullptr;
+  }
+  avgpu_cfg tc = w->cfg;     // the test CPU: mutations off (as avgpu_test_genomes)
+  tc.copy_mut_prob = 0; tc.divide_mut_prob = 0; tc.divide_ins_prob = 0; tc.divide_del_prob = 0;
+  const int64_t n = w->land_chunk;
+  avgpu_world* t = create_world(&tc, w->device, n, true);
+  if (!t) return AVGPU_ENOMEM;
+  t->time_every = 0;         // its interpreter phases are not bracketed: the call times itself
+  LandScratch S = {};
+  S.chunk = n;
+  int rc = t->alloc(&S.budget, (size_t)n);
+  if (rc == 0) rc = t->alloc(&S.fit, (size_t)n);
+  if (rc == 0) rc = t->alloc(&S.dep, (size_t)n);
+  if (rc == 0) rc = t->alloc(&S.count, 2);
+  for (int d = 0; d < 2 && rc == 0; d++) {
+    if ((rc = t->alloc(&S.src[d], (size_t)n)) < 0) break;
+    if ((rc = t->alloc(&S.glen[d], (size_t)n)) < 0) break;
+    rc = t->alloc(&S.gen[d], (size_t)n * TAPE_SLOT);
+  }
+  if (rc == 0 && hipStreamSynchronize(t->stream) != hipSuccess) rc = fail(AVGPU_EHIP, "landscape scratch");
+  for (hipEvent_t& e : w->ev_land)
+    if (rc == 0 && !e && hipEventCreate(&e) != hipSuccess) rc = fail(AVGPU_EHIP, "event creation failed");
+  if (rc < 0) {
+    const std::string e = g_err;
+    avgpu_destroy(t);
+    g_err = e;
+    return rc;
+  }
+  w->land = t;
+  w->land_s = S;
+  return 0;
+}
+
+int avgpu_set_landscape_chunk(avgpu_world* w, int64_t cells) {
+  if (!w) return fail(AVGPU_EINVAL, "NULL world");
+  if (cells <= 0 || cells % LAND_TILE != 0 || cells > (1ll << 30))
+    return fail(AVGPU_EINVAL, "landscape chunk: a positive multiple of 256 cells, at most 2^30");
+  w->land_chunk = cells;      // the scratch world follows at the next avgpu_landscapes
+  return 0;
+}
+
+int avgpu_last_landscape_ms(avgpu_world* w, double* device_ms, int64_t* mutants, int64_t* gestations) {
+  if (!w) return fail(AVGPU_EINVAL, "NULL world");
+  if (device_ms) *device_ms = w->land_ms;
+  if (mutants) *mutants = w->land_mutants;
+  if (gestations) *gestations = w->land_runs;
+  return 0;
+}
+
+int avgpu_landscapes(avgpu_world* w, int n, const uint8_t* genomes, const int32_t* lens, int distance,
+                     avgpu_landscape* out, int32_t* site_count, double* fitness_chart) {
+  int rc = ready(w);
+  if (rc < 0) return rc;
+  if (n <= 0 || !genomes || !lens || !out) return fail(AVGPU_EINVAL, "avgpu_landscapes: n <= 0 or a NULL argument");
+  if (distance != 1 && distance != 2) return fail(AVGPU_EINVAL, "avgpu_landscapes: distance must be 1 or 2");
+  if (fitness_chart && distance != 1) return fail(AVGPU_EINVAL, "avgpu_landscapes: the fitness chart is distance 1 only");
+  const int I = w->n_ops;
+  const int64_t K = I - 1;
+  if (I < 2) return fail(AVGPU_EINVAL, "avgpu_landscapes: an instruction set of one instruction has no mutants");
+  if (w->cfg.test_cpu_time_mod < 0 || w->cfg.test_cpu_time_mod > (BUDGET_PRIM - 1) / AVGPU_MAX_GENOME)
+    return fail(AVGPU_EINVAL, "avgpu_landscapes: TEST_CPU_TIME_MOD x genome length outside [0, 2^30)");
+  // the mutants of the n genomes back to back, their tiles, their sites
+  std::vector<int64_t> base_off((size_t)n), mut_off((size_t)n + 1), tile_off((size_t)n + 1), site_off((size_t)n);
+  std::vector<uint8_t> base_op, base_code;
+  {
+    size_t in = 0;
+    int64_t m = 0, t = 0, s = 0;
+    for (int g = 0; g < n; g++) {
+      const int64_t L = lens[g];
+      if (L < 1 || L > AVGPU_MAX_GENOME) return fail(AVGPU_EINVAL, "avgpu_landscapes: genome length out of range");
+      const int64_t cnt = distance == 1 ? L * K : L * (L - 1) / 2 * K * K;
+      base_off[g] = (int64_t)base_op.size();
+      mut_off[g] = m; tile_off[g] = t; site_off[g] = s;
+      if (__builtin_add_overflow(m, cnt, &m)) return fail(AVGPU_EINVAL, "avgpu_landscapes: the mutant count overflows int64");
+      t += (cnt + LAND_TILE - 1) / LAND_TILE;
+      s += L;
+      for (int64_t k = 0; k < L; k++) {
+        const uint8_t op = genomes[in + (size_t)k];
+        if (op >= I) return fail(AVGPU_EINVAL, "avgpu_landscapes: genome op outside the instruction set");
+        base_op.push_back(op);
+        base_code.push_back(w->op2code[op]);
+      }
+      in += (size_t)L;
+      while (base_op.size() & 15) { base_op.push_back(0); base_code.push_back(0); }   // 16-B groups
+    }
+    mut_off[n] = m; tile_off[n] = t;
+  }
+  const int64_t total = mut_off[n], tiles = tile_off[n], sites = site_off[n - 1] + lens[n - 1];
+  if ((rc = land_alloc(w)) < 0) return rc;
+  avgpu_world* t = w->land;
+  LandScratch S = w->land_s;
+  // the scratch world runs in this world's stream order, with its tables
+  t->stream = w->stream;
+  struct Restore { avgpu_world* t; ~Restore() { t->stream = t->own_stream; } } restore{t};
+  if ((rc = copy_tables(t, w)) < 0) return rc;
+  struct DevBufs {
+    std::vector<void*> v;
+    ~DevBufs() { for (void* p : v) hipFree(p); }
+  } bufs;
+  auto dev = [&](auto** p, size_t count, const void* src) -> int {
+    void* q = nullptr;
+    const size_t bytes = std::max<size_t>(count * sizeof(**p), 16);
+    if (hipMalloc(&q, bytes) != hipSuccess) return fail(AVGPU_ENOMEM, "avgpu_landscapes: hipMalloc");
+    bufs.v.push_back(q);
+    *p = reinterpret_cast<std::remove_reference_t<decltype(*p)>>(q);
+    if (src) HIPCHK(hipMemcpyAsync(q, src, count * sizeof(**p), hipMemcpyHostToDevice, w->stream));
+    else HIPCHK(hipMemsetAsync(q, 0, bytes, w->stream));
+    return 0;
+  };
+  uint8_t *d_op = nullptr, *d_code = nullptr, *d_o2c = nullptr;
+  int64_t *d_boff = nullptr, *d_moff = nullptr, *d_toff = nullptr, *d_soff = nullptr;
+  int32_t* d_len = nullptr;
+  S.n = n; S.num_insts = I; S.time_mod = w->cfg.test_cpu_time_mod;
+  if ((rc = dev(&d_op, base_op.size(), base_op.data())) < 0 || (rc = dev(&d_code, base_code.size(), base_code.data())) < 0 ||
+      (rc = dev(&d_boff, (size_t)n, base_off.data())) < 0 || (rc = dev(&d_len, (size_t)n, lens)) < 0 ||
+      (rc = dev(&d_moff, (size_t)n + 1, mut_off.data())) < 0 || (rc = dev(&d_toff, (size_t)n + 1, tile_off.data())) < 0 ||
+      (rc = dev(&d_soff, (size_t)n, site_off.data())) < 0 || (rc = dev(&d_o2c, AVGPU_MAX_INST, w->op2code)) < 0 ||
+      (rc = dev(&S.base_fit, (size_t)n, nullptr)) < 0 || (rc = dev(&S.base_merit, (size_t)n, nullptr)) < 0 ||
+      (rc = dev(&S.base_gest, (size_t)n, nullptr)) < 0 || (rc = dev(&S.parts, (size_t)tiles, nullptr)) < 0 ||
+      (rc = dev(&S.rows, (size_t)n, nullptr)) < 0 || (rc = dev(&S.site_count, (size_t)sites, nullptr)) < 0 ||
+      (fitness_chart && (rc = dev(&S.chart, (size_t)sites * I, nullptr)) < 0))
+    return rc;
+  S.base_op = d_op; S.base_code = d_code; S.base_off = d_boff; S.len = d_len;
+  S.mut_off = d_moff; S.tile_off = d_toff; S.site_off = d_soff; S.op2code = d_o2c;
+  int64_t runs = 0;
+  // cells [0, cnt) run mutants m0 .. m0 + cnt - 1 (distance 0: base genomes)
+  // through the recursion: depth d's survivors are depth d + 1's cells
+  auto run_chunk = [&](int dist, int64_t m0, int cnt) -> int {
+    HIPCHK(hipMemsetAsync(S.count, 0, 2 * sizeof(int32_t), w->stream));
+    launch_land_seed(t->W, S, w->stream, dist, m0, cnt);
+    int cntd = cnt;
+    for (int depth = 0; depth < 3 && cntd > 0; depth++) {
+      if (depth > 0) launch_land_seed_next(t->W, S, w->stream, depth, cntd);
+      launch_reset_counts(t->W, w->stream);
+      launch_classify_uniform(t->W, w->stream, 0, cntd, S.budget, 0);
+      HIPCHK(hipGetLastError());
+      const int irc = interpret(t, AVGPU_MODE_TEST, 0, cntd);
+      if (irc < 0) return irc;
+      launch_land_judge(t->W, S, w->stream, dist, depth, m0, cntd);
+      HIPCHK(hipGetLastError());
+      runs += cntd;
+      if (depth == 2) break;
+      int32_t next = 0;
+      COPY_SYNC(w, &next, S.count + depth, sizeof(next), hipMemcpyDeviceToHost);
+      cntd = next;
+    }
+    return 0;
+  };
+  HIPCHK(hipEventRecord(w->ev_land[0], w->stream));
+  for (int64_t m0 = 0; m0 < n; m0 += S.chunk)
+    if ((rc = run_chunk(0, m0, (int)std::min<int64_t>(S.chunk, n - m0))) < 0) return rc;
+  runs = 0;                                  // (the base genomes' runs are not the landscape's)
+  {
+    int g = 0;                               // the genome holding the chunk's end
+    int64_t m0 = 0, t0 = 0;
+    while (m0 < total) {
+      // the chunk ends at the last tile boundary within S.chunk mutants
+      int64_t m1 = total, t1 = tiles;
+      if (m0 + S.chunk < total) {
+        while (mut_off[(size_t)g + 1] <= m0 + S.chunk) g++;
+        const int64_t full = (m0 + S.chunk - mut_off[g]) / LAND_TILE;
+        m1 = mut_off[g] + full * LAND_TILE;
+        t1 = tile_off[g] + full;
+      }
+      if ((rc = run_chunk(distance, m0, (int)(m1 - m0))) < 0) return rc;
+      launch_land_reduce(S, w->stream, distance, m0, t0, t1);
+      HIPCHK(hipGetLastError());
+      m0 = m1; t0 = t1;
+    }
+  }
+  launch_land_rows(S, w->stream, distance);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(w->ev_land[1], w->stream));
+  std::vector<avgpu_landscape> rows((size_t)n);
+  std::vector<int32_t> sc((size_t)sites);
+  std::vector<double> chart(fitness_chart ? (size_t)sites * I : 0);
+  HIPCHK(hipMemcpyAsync(rows.data(), S.rows, rows.size() * sizeof(avgpu_landscape), hipMemcpyDeviceToHost, w->stream));
+  HIPCHK(hipMemcpyAsync(sc.data(), S.site_count, sc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, w->stream));
+  if (fitness_chart)
+    HIPCHK(hipMemcpyAsync(chart.data(), S.chart, chart.size() * sizeof(double), hipMemcpyDeviceToHost, w->stream));
+  HIPCHK(hipStreamSynchronize(w->stream));
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, w->ev_land[0], w->ev_land[1]));
+  w->land_ms = ms;
+  w->land_mutants = total;
+  w->land_runs = runs;
+  // cLandscape::Process (main/cLandscape.cc:158-169): a site's entropy is the
+  // log of its legal states, the unmutated one included; ProcessDump's chart
+  // holds the base fitness at the original instruction
+  const double max_ent = std::log((double)I);
+  for (int g = 0; g < n; g++) {
+    avgpu_landscape& r = rows[(size_t)g];
+    double ent = 0.0;
+    for (int64_t k = 0; k < lens[g]; k++) {
+      const size_t site = (size_t)(site_off[g] + k);
+      ent += std::log((double)sc[site] + 1) / max_ent;
+      if (fitness_chart) chart[site * I + base_op[(size_t)(base_off[g] + k)]] = r.base_fitness;
+    }
+    r.total_entropy = ent;
+    r.complexity = (double)lens[g] - ent;
+  }
+  memcpy(out, rows.data(), rows.size() * sizeof(avgpu_landscape));
+  if (site_count) memcpy(site_count, sc.data(), sc.size() * sizeof(int32_t));
+  if (fitness_chart) memcpy(fitness_chart, chart.data(), chart.size() * sizeof(double));
   return 0;
 }
 

@@ -817,6 +817,59 @@ __device__ __forceinline__ int size_merit(int method, int base_const, int glen, 
 __device__ __forceinline__ int calc_size_merit(const DevWorld& W, int glen, int copied, int exe) {
   return size_merit(W.base_merit_method, W.base_const_merit, glen, copied, exe);
 }
+// An organism injected into cell c, whose tape already holds its len sites in
+// canonical codes: cPopulation::Inject / ActivateOrganism +
+// cPhenotype::SetupInject (main/cPhenotype.cc:599-640).  in3: the cell's three
+// inputs, or NULL for the test-CPU constants (deterministic) or a draw from
+// the cell's stream.  One lane per cell; k_set_orgs and the landscape's seed
+// kernels (landscape.hip) both initialise an organism through it.
+__device__ __forceinline__ void inject_org(const DevWorld& W, int64_t c, int len, double merit, const int32_t* in3,
+                                           int deterministic) {
+  const int64_t N = W.n;
+  const uint8_t* t = W.tape + c * TAPE_SLOT;
+  // registers, heads, label, counters, buffers, task counts, stacks: zero
+  int32_t* x = W.xs + c * XS_WORDS;
+  for (int k = 0; k < XS_WORDS; k++) x[k] = 0;
+  W.ctl[c] = CTL_ALIVE;
+  W.mem_size[c] = len;
+  int mx = 0;
+  if (W.death_method > 0) {                 // cOrganism::initialize (main/cOrganism.cc:216-236)
+    mx = W.age_limit;
+    if (W.death_method == 2) mx *= len;
+    if (mx < 1) mx = 1;
+  }
+  W.max_exec[c] = mx;
+  W.birth_len[c] = len;
+  if (W.track_age) W.age[c] = -1;          // injected between updates: age 0 during the next one
+  W.gkey[c] = gk_tape(t, len);
+  // stream key (DESIGN.md RNG spec)
+  uint32_t lo, hi, ctr = 0;
+  derive_key(W.seed_lo, W.seed_hi, (uint32_t)(W.cell0 + c), 0xA5A5A5A5U, lo, hi);
+  int in0, in1, in2;
+  if (in3) { in0 = in3[0]; in1 = in3[1]; in2 = in3[2]; }
+  else if (deterministic) { in0 = 0x0f13149f; in1 = 0x3308e53e; in2 = 0x556241eb; }
+  else {                                      // cEnvironment::SetupInputs random
+    in0 = (15 << 24) + (int)rng_below(lo, hi, ctr, 1u << 24);
+    in1 = (51 << 24) + (int)rng_below(lo, hi, ctr, 1u << 24);
+    in2 = (85 << 24) + (int)rng_below(lo, hi, ctr, 1u << 24);
+  }
+  W.rng[c] = lo; W.rng[N + c] = hi; W.rng[2 * N + c] = ctr;
+  if (W.rec_off) W.rec_off[c] = -1;   // a new organism draws from its counter stream
+  if (W.spec) W.spec[c] = 0;           // serial world: no speculative credit yet
+  W.inputs[c] = in0; W.inputs[N + c] = in1; W.inputs[2 * N + c] = in2;
+  W.budget[c] = 0;
+  for (int k = 0; k < AVGPU_MAX_REACTIONS; k++) {
+    W.last_task[k * N + c] = 0; W.cur_react[k * N + c] = 0;   // record words: zeroed above
+  }
+  // cPhenotype::SetupInject (main/cPhenotype.cc:599-640)
+  *reinterpret_cast<double*>(x + XS_BONUS) = W.default_bonus;
+  W.merit[c] = merit > 0.0 ? merit : (double)len;
+  W.fitness[c] = 0.0;
+  W.credit[c] = 0.0;
+  W.gest_time[c] = 0; W.num_div[c] = 0; W.generation[c] = 0;
+  W.copied[c] = len; W.child_copied[c] = 0; W.executed[c] = len;
+}
+
 // a value the compiler must keep (in an SGPR, or spilled) rather than
 // re-load from its invariant source at each use
 #define OPQ(x) asm("" : "+s"(x))
@@ -952,6 +1005,60 @@ struct GtScratch {
 };
 void launch_genotype_group(const DevWorld& W, const GtScratch& S, hipStream_t s);
 void launch_genotype_rows(const DevWorld& W, const GtScratch& S, avgpu_genotype* d_out, hipStream_t s);
+// mutational landscapes (landscape.hip).  The mutants of every
+// base genome are numbered back to back: mutant m of the call is rank
+// m - mut_off[g] of genome g.  Ranks are cut into tiles of LAND_TILE aligned
+// to each genome's rank 0 (a genome's last tile may be short); a chunk of the
+// scratch test world holds whole tiles, packed densely across genomes.
+#define LAND_TILE 256
+// what a tile of ranks, or a genome's tiles, add up to
+struct LandPart {
+  double sf, sq, sp, sn;    // sums of fitness, its square, beneficial and deleterious fitness
+  double pf;                // peak: the largest beneficial fitness (-1: none) ...
+  int64_t pr;               // ... and the lowest rank attaining it
+  int32_t dead, neg, neut, pos;
+  int32_t run1, run2;       // mutants run at recursion depth 1, 2
+  int64_t pad;
+};
+static_assert(sizeof(LandPart) == 80, "LandPart");
+struct LandScratch {
+  int64_t chunk;            // cells of the scratch test world
+  // the call's inputs (uploaded per call)
+  int32_t n, num_insts, time_mod, pad0;
+  const uint8_t* base_op;   // base genomes in op codes, genome g at base_off[g] (16-B aligned, zero padded)
+  const uint8_t* base_code; // the same in canonical codes
+  const int64_t* base_off;  // [n]
+  const int32_t* len;       // [n]
+  const int64_t* mut_off;   // [n + 1] mutants before genome g
+  const int64_t* tile_off;  // [n + 1] tiles before genome g
+  const int64_t* site_off;  // [n] sites before genome g (site_count / chart rows)
+  const uint8_t* op2code;   // [AVGPU_MAX_INST]
+  // per genome
+  double* base_fit;         // [n] ProcessBase: colony fitness,
+  double* base_merit;       // colony organism's merit,
+  int32_t* base_gest;       // its gestation time
+  LandPart* parts;          // [tiles]
+  avgpu_landscape* rows;    // [n]
+  int32_t* site_count;      // [sites] or NULL
+  double* chart;            // [sites][num_insts] or NULL
+  // per chunk (kept with the scratch world)
+  int32_t* budget;          // [chunk] budget row of the depth being run
+  double* fit;              // [chunk] colony fitness of the chunk's mutant i
+  uint8_t* dep;             // [chunk] the depth its verdict fell at
+  int32_t* src[2];          // [chunk] depth d + 1's cell j runs the offspring of depth d's cell src[d][j]
+  uint8_t* gen[2];          // [chunk][TAPE_SLOT] the genome depth d + 1's cell j runs
+  int32_t* glen[2];         // [chunk] its length
+  int32_t* count;           // [2] survivors listed for depth 1, 2
+};
+// cells [0, cnt) take the chunk's mutants m0 .. m0 + cnt - 1 (distance 0: the base genomes themselves)
+void launch_land_seed(const DevWorld& W, const LandScratch& S, hipStream_t s, int distance, int64_t m0, int cnt);
+// cells [0, cnt) take the offspring listed for depth 1 or 2
+void launch_land_seed_next(const DevWorld& W, const LandScratch& S, hipStream_t s, int depth, int cnt);
+void launch_land_judge(const DevWorld& W, const LandScratch& S, hipStream_t s, int distance, int depth, int64_t m0,
+                       int cnt);
+// tiles [t0, t1) of the chunk that starts at mutant m0
+void launch_land_reduce(const LandScratch& S, hipStream_t s, int distance, int64_t m0, int64_t t0, int64_t t1);
+void launch_land_rows(const LandScratch& S, hipStream_t s, int distance);
 void launch_merit_total(const DevWorld& W, hipStream_t s, double* d_totals, double* d_scratch);
 // strip tiles
 void launch_tile_partials(const DevWorld& W, hipStream_t s, double* d_out, int reset);

@@ -105,53 +105,12 @@ __global__ void k_set_orgs(DevWorld W, int64_t first, int64_t count, const uint8
                            const int32_t* inputs, int deterministic) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= count) return;
-  const int64_t N = W.n;
   const int64_t c = first + i;
   const int len = lens[i];
   const uint8_t* g = codes + offsets[i];
   uint8_t* t = W.tape + c * TAPE_SLOT;
   for (int k = 0; k < len; k++) t[k] = g[k] & CODE_MASK;
-  // registers, heads, label, counters, buffers, task counts, stacks: zero
-  int32_t* x = W.xs + c * XS_WORDS;
-  for (int k = 0; k < XS_WORDS; k++) x[k] = 0;
-  W.ctl[c] = CTL_ALIVE;
-  W.mem_size[c] = len;
-  int mx = 0;
-  if (W.death_method > 0) {                 // cOrganism::initialize (main/cOrganism.cc:216-236)
-    mx = W.age_limit;
-    if (W.death_method == 2) mx *= len;
-    if (mx < 1) mx = 1;
-  }
-  W.max_exec[c] = mx;
-  W.birth_len[c] = len;
-  if (W.track_age) W.age[c] = -1;          // injected between updates: age 0 during the next one
-  W.gkey[c] = gk_tape(t, len);
-  // stream key (DESIGN.md RNG spec)
-  uint32_t lo, hi, ctr = 0;
-  derive_key(W.seed_lo, W.seed_hi, (uint32_t)(W.cell0 + c), 0xA5A5A5A5U, lo, hi);
-  int in0, in1, in2;
-  if (inputs) { in0 = inputs[3 * i]; in1 = inputs[3 * i + 1]; in2 = inputs[3 * i + 2]; }
-  else if (deterministic) { in0 = 0x0f13149f; in1 = 0x3308e53e; in2 = 0x556241eb; }
-  else {                                      // cEnvironment::SetupInputs random
-    in0 = (15 << 24) + (int)rng_below(lo, hi, ctr, 1u << 24);
-    in1 = (51 << 24) + (int)rng_below(lo, hi, ctr, 1u << 24);
-    in2 = (85 << 24) + (int)rng_below(lo, hi, ctr, 1u << 24);
-  }
-  W.rng[c] = lo; W.rng[N + c] = hi; W.rng[2 * N + c] = ctr;
-  if (W.rec_off) W.rec_off[c] = -1;   // a new organism draws from its counter stream
-  if (W.spec) W.spec[c] = 0;           // serial world: no speculative credit yet
-  W.inputs[c] = in0; W.inputs[N + c] = in1; W.inputs[2 * N + c] = in2;
-  W.budget[c] = 0;
-  for (int k = 0; k < AVGPU_MAX_REACTIONS; k++) {
-    W.last_task[k * N + c] = 0; W.cur_react[k * N + c] = 0;   // record words: zeroed above
-  }
-  // cPhenotype::SetupInject (main/cPhenotype.cc:599-640)
-  *reinterpret_cast<double*>(x + XS_BONUS) = W.default_bonus;
-  W.merit[c] = (merits && merits[i] > 0.0) ? merits[i] : (double)len;
-  W.fitness[c] = 0.0;
-  W.credit[c] = 0.0;
-  W.gest_time[c] = 0; W.num_div[c] = 0; W.generation[c] = 0;
-  W.copied[c] = len; W.child_copied[c] = 0; W.executed[c] = len;
+  inject_org(W, c, len, merits ? merits[i] : 0.0, inputs ? inputs + 3 * i : nullptr, deterministic);
 }
 
 // the cHardwareBase inspection tuple of cell c (zero padding: the digest below

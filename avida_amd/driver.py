@@ -102,6 +102,12 @@ class ProductWorld:
         (avgpu_get_genotypes)"""
         return capi.get_genotypes(self.lib, self.h)
 
+    def landscape(self, genomes, distance=1, chart=None):
+        """the full substitution landscapes of `genomes` on the device
+        (avgpu_landscapes): a list of landscape.Landscape"""
+        from . import landscape
+        return landscape.full(self, genomes, distance, chart)
+
     def resources(self, spatial=False):
         lv = (C.c_double * max(1, self.nres))()
         self._call("get_resources", self.h, lv, None)

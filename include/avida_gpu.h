@@ -662,6 +662,53 @@ int avgpu_test_genomes(avgpu_world* w, int n, const uint8_t* genomes, const int3
                        avgpu_test_result* results, char* executed_flags, int flags_cap,
                        uint8_t* offspring);
 
+/* ---- mutational landscapes ------------------------
+ * cLandscape's accumulators for one base genome (main/cLandscape.cc:49-142):
+ * what Reset clears, ProcessBase sets and ProcessGenome adds up. */
+typedef struct avgpu_landscape {
+  int64_t total_count, dead_count, neg_count, neut_count, pos_count;
+  int64_t gestations[3];              /* test-CPU runs at recursion depth 0, 1, 2 (the base's not counted) */
+  int64_t peak_rank;                  /* lowest mutant rank attaining peak_fitness; -1: the base */
+  double base_fitness, base_merit;    /* ProcessBase: colony fitness, colony organism's merit */
+  double peak_fitness, total_fitness, total_sqr_fitness, pos_size, neg_size;
+  double total_entropy, complexity;
+  int32_t base_gestation, distance, genome_length, num_insts;
+} avgpu_landscape;
+/* The full substitution landscape of n genomes at `distance` 1 or 2:
+ * cLandscape::Process (main/cLandscape.cc:144-213; analyze mode's
+ * FullLandscape, PrecalcLandscape) and, with fitness_chart, ProcessDump
+ * (:217-261; DumpLandscape) -- every mutant made on the device, run through
+ * cTestCPU::TestGenome_Body's viability recursion (cpu/cTestCPU.cc:233-326,
+ * generation_tests 3, deterministic inputs, mutations off, TEST_CPU_TIME_MOD x
+ * length instructions per run), classified against the base genome's colony
+ * fitness (ProcessGenome :97-123, FITNESS_NEUTRAL_RANGE 0) and summed up there.
+ * It replaces a loop over avgpu_test_genomes with the recursion on the host.
+ * genomes: op codes packed back to back, lens[i] each.  out: n rows.
+ * Mutant ranks: distance 1, site * (num_insts - 1) + j with j counting the op
+ * codes in ascending order, the original skipped; distance 2, the reference's
+ * recursion order (first site, its op, second site > first, its op, each
+ * ascending).  site_count (sum of lens, or NULL): per site the mutants with
+ * fitness >= base (at distance 2 under their second site, Process_Body:204).
+ * fitness_chart (sum of lens x num_insts doubles, or NULL; distance 1 only):
+ * [site][op] colony fitness, the original op's entry the base fitness.
+ * Stream-ordered behind the queued updates, complete on return; the world,
+ * its random streams and its statistics are not changed.  The double sums
+ * have a fixed shape: the same bytes from every call, chunk
+ * size and batch.  AVGPU_EINVAL (out untouched): distance not 1 or 2, a chart
+ * at distance 2, n <= 0, a length outside 1..AVGPU_MAX_GENOME, an op code
+ * outside the instruction set, a mutant count past int64. */
+int avgpu_landscapes(avgpu_world* w, int n, const uint8_t* genomes, const int32_t* lens,
+                     int distance, avgpu_landscape* out, int32_t* site_count, double* fitness_chart);
+/* Cells of the scratch test world the mutants run through, a positive
+ * multiple of 256 (default 65536; about 13 KiB of device memory per cell,
+ * allocated by the first landscape call, kept until avgpu_destroy and
+ * re-created when this size changes).  No reference equivalent. */
+int avgpu_set_landscape_chunk(avgpu_world* w, int64_t cells);
+/* Timing of the last landscape call (no reference equivalent): the device
+ * time between its first and last kernel in ms (HIP events on the world's
+ * stream), its mutants and its test-CPU runs. */
+int avgpu_last_landscape_ms(avgpu_world* w, double* device_ms, int64_t* mutants, int64_t* gestations);
+
 /* ---- statistics / multi-GPU plumbing ------------------------------------ */
 /* the last update's statistics (reduced here if that update ran with out == NULL) */
 int avgpu_get_stats(avgpu_world* w, avgpu_update_stats* out);
