@@ -177,8 +177,8 @@ def _transfer(src, dst, n, chunk=1 << 16):
 def test_config2_bench_regime_bit_exact(golden):
     """Parity in the regime bench.py times (VERDICT r2 'next' #1): the
     configs[2] world run on the GPU for bench.py's 150 burn-in updates -- an
-    aged world with size-class spills, list classes running beside class 0
-    on the aux streams, sorted windows -- is checkpointed cell by cell
+    aged world with size-class spills, list classes running in the leading
+    blocks of class 0's launch, sorted windows -- is checkpointed cell by cell
     (avgpu_get_states) into the oracle; both then run 3 more updates and
     every counter and every cell digest must agree.  Every birth is placed
     (births_dropped == 0: no queue overflow, no oversize offspring)."""
