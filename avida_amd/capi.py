@@ -227,6 +227,12 @@ LANDSCAPE_DTYPE = np.dtype([("total_count", "<i8"), ("dead_count", "<i8"), ("neg
                             ("complexity", "<f8"), ("base_gestation", "<i4"), ("distance", "<i4"),
                             ("genome_length", "<i4"), ("num_insts", "<i4")])
 assert LANDSCAPE_DTYPE.itemsize == 160
+# avgpu_indel_kind, avgpu_epistasis (cLandscape::TestAllPairs' accumulators)
+LAND_INSERT, LAND_DELETE = 1, 2
+EPISTASIS_DTYPE = np.dtype([("total_epi_count", "<i8"), ("dead_epi_count", "<i8"), ("neg_epi_count", "<i8"),
+                            ("pos_epi_count", "<i8"), ("no_epi_count", "<i8"), ("gestations", "<i8", (3,)),
+                            ("neg_epi_size", "<f8"), ("pos_epi_size", "<f8"), ("no_epi_size", "<f8")])
+assert EPISTASIS_DTYPE.itemsize == 88
 
 
 # C-ABI symbols declared in include/avida_gpu.h (checked by tests/test_capi.py)
@@ -245,6 +251,7 @@ EXPORTED = [
     "avgpu_get_serial_state", "avgpu_set_serial_state", "avgpu_set_timing",
     "avgpu_get_genotypes", "avgpu_last_genotypes_ms",
     "avgpu_landscapes", "avgpu_set_landscape_chunk", "avgpu_last_landscape_ms",
+    "avgpu_landscapes_indel", "avgpu_landscape_pairs",
 ]
 
 
@@ -499,6 +506,12 @@ def load_product(path=None):
     lib.avgpu_landscapes.restype = C.c_int
     lib.avgpu_landscapes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int,
                                      C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
+    lib.avgpu_landscapes_indel.restype = C.c_int
+    lib.avgpu_landscapes_indel.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int,
+                                           C.c_void_p, C.POINTER(C.c_int32)]
+    lib.avgpu_landscape_pairs.restype = C.c_int
+    lib.avgpu_landscape_pairs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
+                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
     lib.avgpu_set_landscape_chunk.restype = C.c_int
     lib.avgpu_set_landscape_chunk.argtypes = [C.c_void_p, C.c_int64]
     lib.avgpu_last_landscape_ms.restype = C.c_int

@@ -1011,6 +1011,10 @@ void launch_genotype_rows(const DevWorld& W, const GtScratch& S, avgpu_genotype*
 // to each genome's rank 0 (a genome's last tile may be short); a chunk of the
 // scratch test world holds whole tiles, packed densely across genomes.
 #define LAND_TILE 256
+// how a rank becomes a mutant: the base genome itself, one or two
+// substitutions (cLandscape::Process_Body), one insertion (ProcessInsert),
+// one deletion (ProcessDelete)
+enum { LAND_BASE = 0, LAND_SUB1 = 1, LAND_SUB2 = 2, LAND_INS = 3, LAND_DEL = 4 };
 // what a tile of ranks, or a genome's tiles, add up to
 struct LandPart {
   double sf, sq, sp, sn;    // sums of fitness, its square, beneficial and deleterious fitness
@@ -1021,17 +1025,26 @@ struct LandPart {
   int64_t pad;
 };
 static_assert(sizeof(LandPart) == 80, "LandPart");
+// ... and what a tile of pair mutants adds up to (cLandscape::TestMutPair)
+struct LandEpiPart {
+  double sn, sp, s0;        // sums of combo fitness: antagonistic, synergistic, no epistasis
+  int64_t dead, neg, pos, none;
+  int64_t run1, run2;       // pair mutants run at recursion depth 1, 2
+};
+static_assert(sizeof(LandEpiPart) == 72, "LandEpiPart");
 struct LandScratch {
   int64_t chunk;            // cells of the scratch test world
   // the call's inputs (uploaded per call)
   int32_t n, num_insts, time_mod, pad0;
-  const uint8_t* base_op;   // base genomes in op codes, genome g at base_off[g] (16-B aligned, zero padded)
+  const uint8_t* base_op;   // base genomes in op codes, genome g at base_off[g] (16-B aligned, zero padded,
+                            // one zero group behind the last genome)
   const uint8_t* base_code; // the same in canonical codes
   const int64_t* base_off;  // [n]
   const int32_t* len;       // [n]
   const int64_t* mut_off;   // [n + 1] mutants before genome g
   const int64_t* tile_off;  // [n + 1] tiles before genome g
-  const int64_t* site_off;  // [n] sites before genome g (site_count / chart rows)
+  const int64_t* site_off;  // [n] sites before genome g (site_count / chart rows; an insertion
+                            // landscape has len + 1 of them per genome)
   const uint8_t* op2code;   // [AVGPU_MAX_INST]
   // per genome
   double* base_fit;         // [n] ProcessBase: colony fitness,
@@ -1041,6 +1054,8 @@ struct LandScratch {
   avgpu_landscape* rows;    // [n]
   int32_t* site_count;      // [sites] or NULL
   double* chart;            // [sites][num_insts] or NULL
+  LandEpiPart* eparts;      // [tiles] of the pair mutants (avgpu_landscape_pairs)
+  avgpu_epistasis* erows;   // [n]
   // per chunk (kept with the scratch world)
   int32_t* budget;          // [chunk] budget row of the depth being run
   double* fit;              // [chunk] colony fitness of the chunk's mutant i
@@ -1050,15 +1065,19 @@ struct LandScratch {
   int32_t* glen[2];         // [chunk] its length
   int32_t* count;           // [2] survivors listed for depth 1, 2
 };
-// cells [0, cnt) take the chunk's mutants m0 .. m0 + cnt - 1 (distance 0: the base genomes themselves)
-void launch_land_seed(const DevWorld& W, const LandScratch& S, hipStream_t s, int distance, int64_t m0, int cnt);
+// cells [0, cnt) take the chunk's mutants m0 .. m0 + cnt - 1 (mode LAND_*; LAND_BASE: the base genomes themselves)
+void launch_land_seed(const DevWorld& W, const LandScratch& S, hipStream_t s, int mode, int64_t m0, int cnt);
 // cells [0, cnt) take the offspring listed for depth 1 or 2
 void launch_land_seed_next(const DevWorld& W, const LandScratch& S, hipStream_t s, int depth, int cnt);
-void launch_land_judge(const DevWorld& W, const LandScratch& S, hipStream_t s, int distance, int depth, int64_t m0,
+void launch_land_judge(const DevWorld& W, const LandScratch& S, hipStream_t s, int mode, int depth, int64_t m0,
                        int cnt);
 // tiles [t0, t1) of the chunk that starts at mutant m0
-void launch_land_reduce(const LandScratch& S, hipStream_t s, int distance, int64_t m0, int64_t t0, int64_t t1);
+void launch_land_reduce(const LandScratch& S, hipStream_t s, int mode, int64_t m0, int64_t t0, int64_t t1);
+// distance: the value the rows report (cLandscape's `distance` member)
 void launch_land_rows(const LandScratch& S, hipStream_t s, int distance);
+// the pair mutants' tiles [t0, t1) against S.chart, and their rows
+void launch_land_epi_reduce(const LandScratch& S, hipStream_t s, int64_t m0, int64_t t0, int64_t t1);
+void launch_land_epi_rows(const LandScratch& S, hipStream_t s);
 void launch_merit_total(const DevWorld& W, hipStream_t s, double* d_totals, double* d_scratch);
 // strip tiles
 void launch_tile_partials(const DevWorld& W, hipStream_t s, double* d_out, int reset);

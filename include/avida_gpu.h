@@ -699,14 +699,63 @@ typedef struct avgpu_landscape {
  * outside the instruction set, a mutant count past int64. */
 int avgpu_landscapes(avgpu_world* w, int n, const uint8_t* genomes, const int32_t* lens,
                      int distance, avgpu_landscape* out, int32_t* site_count, double* fitness_chart);
+/* The insertion or deletion landscape of n genomes: cLandscape::ProcessInsert
+ * (main/cLandscape.cc:297-330; analyze mode's InsertionLandscape,
+ * actions/LandscapeActions.cc:333-457) and ProcessDelete (:265-295;
+ * DeletionLandscape).  Every mutant is made, run, judged and summed up as in
+ * avgpu_landscapes; only its genome differs.
+ * AVGPU_LAND_INSERT: mutant rank = line * num_insts + op, line 0..L (L: behind
+ * the last site), op 0..num_insts-1, no op skipped: (L + 1) * num_insts mutants
+ * of L + 1 sites.  site_count has L + 1 entries per genome (Reset, :49-95,
+ * allocates size + 1; ProcessInsert counts under line_num).
+ * AVGPU_LAND_DELETE: rank = the removed line, 0..L-1: L mutants of L - 1
+ * sites; L site_count entries per genome.
+ * Rows as avgpu_landscapes' with distance 1 (the actions' default, which
+ * PrintStats prints), total_entropy and complexity 0 (neither function
+ * computes them).  Stream order, determinism and the untouched world as for
+ * avgpu_landscapes.  AVGPU_EINVAL (out untouched): what avgpu_landscapes
+ * refuses, a kind other than these two, the insertion landscape of a genome
+ * of AVGPU_MAX_GENOME sites, the deletion landscape of a one-site genome. */
+enum avgpu_indel_kind { AVGPU_LAND_INSERT = 1, AVGPU_LAND_DELETE = 2 };
+int avgpu_landscapes_indel(avgpu_world* w, int n, const uint8_t* genomes, const int32_t* lens,
+                           int kind, avgpu_landscape* out, int32_t* site_count);
+/* cLandscape::TestAllPairs' accumulators (main/cLandscape.cc:71-79, :934-946) */
+typedef struct avgpu_epistasis {
+  int64_t total_epi_count, dead_epi_count, neg_epi_count, pos_epi_count, no_epi_count;
+  int64_t gestations[3];                       /* test-CPU runs of the pair mutants at depth 0, 1, 2 */
+  double neg_epi_size, pos_epi_size, no_epi_size;
+} avgpu_epistasis;
+/* cLandscape::TestAllPairs (main/cLandscape.cc:788-825; analyze mode's
+ * PairTestLandscape with sample_size 0, actions/LandscapeActions.cc:772-829)
+ * for n genomes.  ProcessBase first; a genome whose base fitness is 0 stops
+ * there (:793): its `out` row keeps base_*, genome_length and num_insts with
+ * every count and sum 0, its `epi` row is all zero, its chart holds 0.
+ * Otherwise BuildFitnessChart (:709-743), a one-step pass through
+ * ProcessGenome: `out` is avgpu_landscapes' distance-1 row with distance 0
+ * and no entropy (Reset's values, which PrintStats prints), fitness_chart
+ * (sum of lens x num_insts doubles, or NULL) its [site][op] table.  Then
+ * every pair of substitutions -- sites s1 < s2, ops other than the base's:
+ * C(L,2) * (num_insts-1)^2 mutants, numbered as distance-2 ranks -- is run
+ * through the viability recursion and classified by TestMutPair (:909-949)
+ * in IEEE doubles, in this order: combo = f12 / base, m1 = chart[s1][k1] /
+ * base, m2 = chart[s2][k2] / base, mult = m1 * m2; dead if (m1 == 0 || m2 ==
+ * 0) && combo == 0, else antagonistic (neg, size += combo) if combo < mult,
+ * else synergistic (pos) if combo > mult, else none.  The pair mutants enter
+ * `epi` only (TestMutPair calls TestGenome, not ProcessGenome).  The three
+ * sizes are summed in the fixed shape of DESIGN.md 13.  AVGPU_EINVAL (outputs
+ * untouched): what avgpu_landscapes refuses, a one-site genome. */
+int avgpu_landscape_pairs(avgpu_world* w, int n, const uint8_t* genomes, const int32_t* lens,
+                          avgpu_landscape* out, avgpu_epistasis* epi, double* fitness_chart);
 /* Cells of the scratch test world the mutants run through, a positive
  * multiple of 256 (default 65536; about 13 KiB of device memory per cell,
  * allocated by the first landscape call, kept until avgpu_destroy and
  * re-created when this size changes).  No reference equivalent. */
 int avgpu_set_landscape_chunk(avgpu_world* w, int64_t cells);
-/* Timing of the last landscape call (no reference equivalent): the device
- * time between its first and last kernel in ms (HIP events on the world's
- * stream), its mutants and its test-CPU runs. */
+/* Timing of the last landscape call -- avgpu_landscapes,
+ * avgpu_landscapes_indel or avgpu_landscape_pairs -- (no reference
+ * equivalent): the device time between its first and last kernel in ms (HIP
+ * events on the world's stream), its mutants and its test-CPU runs (for the
+ * pairs: the one-step and the pair mutants together). */
 int avgpu_last_landscape_ms(avgpu_world* w, double* device_ms, int64_t* mutants, int64_t* gestations);
 
 /* ---- statistics / multi-GPU plumbing ------------------------------------ */
