@@ -217,6 +217,69 @@ def get_genotypes(lib, handle):
         cap = lib._genotype_cap = int(totals.num_genotypes) + int(totals.num_genotypes) // 4 + 16
 
 
+# avgpu_arbiter_row (include/avida_gpu.h): one row per active genotype, keys
+# ascending; row j describes row j of the genotype table
+ARBITER_ROW_DTYPE = np.dtype([("genotype_key", "<u8"), ("id", "<i8"), ("update_born", "<i8"),
+                              ("total_units", "<i8"), ("num_units", "<i4"), ("genome_length", "<i4"),
+                              ("name_no", "<i4"), ("threshold", "<i4")])
+assert ARBITER_ROW_DTYPE.itemsize == 48
+# avgpu_arbiter_summary: what one classification returns
+ARBITER_SUMMARY_DTYPE = np.dtype([("update", "<i8"), ("num_organisms", "<i8"), ("num_genotypes", "<i8"),
+                                  ("num_threshold", "<i8"), ("tot_genotypes", "<i8"), ("tot_threshold", "<i8"),
+                                  ("next_id", "<i8"), ("num_new", "<i8"), ("num_gone", "<i8"),
+                                  ("num_crossed", "<i8"), ("sum_copied_size", "<i8"),
+                                  ("sum_executed_size", "<i8"), ("dominant_row", "<i8"),
+                                  ("dominant_state", ARBITER_ROW_DTYPE), ("dominant", GENOTYPE_DTYPE)])
+assert ARBITER_SUMMARY_DTYPE.itemsize == 232
+
+
+def _arbiter_check(lib, rc, name):
+    if rc < 0:
+        raise RuntimeError(f"{name}: {lib.avgpu_last_error().decode()}")
+    return rc
+
+
+def classify_genotypes(lib, handle, update, threshold):
+    """One classification on the device (avgpu_classify_genotypes): its
+    summary, one ARBITER_SUMMARY_DTYPE record"""
+    out = np.zeros(1, dtype=ARBITER_SUMMARY_DTYPE)
+    _arbiter_check(lib, lib.avgpu_classify_genotypes(handle, int(update), int(threshold),
+                                                     out.ctypes.data_as(C.c_void_p)), "avgpu_classify_genotypes")
+    return out[0]
+
+
+def get_arbiter(lib, handle, rows_hint=0):
+    """(rows, table, summary, sz_count) of the last classification through
+    avgpu_get_arbiter: ARBITER_ROW_DTYPE and GENOTYPE_DTYPE rows, keys
+    ascending, the summary record and the AVGPU_MAX_GENOME + 1 name counters"""
+    summary = np.zeros(1, dtype=ARBITER_SUMMARY_DTYPE)
+    sz = np.zeros(MAX_GENOME + 1, dtype=np.int64)
+    _arbiter_check(lib, lib.avgpu_get_arbiter(handle, None, None, 0, summary.ctypes.data_as(C.c_void_p),
+                                              sz.ctypes.data_as(C.c_void_p)), "avgpu_get_arbiter")
+    m = int(summary[0]["num_genotypes"])
+    rows = np.zeros(m, dtype=ARBITER_ROW_DTYPE)
+    table = np.zeros(m, dtype=GENOTYPE_DTYPE)
+    if m:
+        rc = _arbiter_check(lib, lib.avgpu_get_arbiter(handle, rows.ctypes.data_as(C.c_void_p),
+                                                       table.ctypes.data_as(C.c_void_p), m, None, None),
+                            "avgpu_get_arbiter")
+        assert rc == m
+    return rows, table, summary[0], sz
+
+
+def set_arbiter(lib, handle, rows, summary, sz_count):
+    """Install an arbiter state (avgpu_set_arbiter): resume or hand-over"""
+    rows = np.ascontiguousarray(rows, dtype=ARBITER_ROW_DTYPE)
+    summary = np.ascontiguousarray(np.asarray(summary, dtype=ARBITER_SUMMARY_DTYPE).reshape(1))
+    sz = None if sz_count is None else np.ascontiguousarray(sz_count, dtype=np.int64)
+    if sz is not None and len(sz) != MAX_GENOME + 1:
+        raise ValueError("sz_count holds AVGPU_MAX_GENOME + 1 counters")
+    _arbiter_check(lib, lib.avgpu_set_arbiter(handle, len(rows), rows.ctypes.data_as(C.c_void_p),
+                                              summary.ctypes.data_as(C.c_void_p),
+                                              None if sz is None else sz.ctypes.data_as(C.c_void_p)),
+                   "avgpu_set_arbiter")
+
+
 # avgpu_landscape (include/avida_gpu.h): one row per base genome
 MAX_INST = 64
 LANDSCAPE_DTYPE = np.dtype([("total_count", "<i8"), ("dead_count", "<i8"), ("neg_count", "<i8"),
@@ -250,6 +313,8 @@ EXPORTED = [
     "avgpu_state_digests", "avgpu_set_rng_mode", "avgpu_run_serial_updates", "avgpu_set_serial_streams",
     "avgpu_get_serial_state", "avgpu_set_serial_state", "avgpu_set_timing",
     "avgpu_get_genotypes", "avgpu_last_genotypes_ms",
+    "avgpu_classify_genotypes", "avgpu_get_arbiter", "avgpu_set_arbiter", "avgpu_reset_arbiter",
+    "avgpu_last_arbiter_ms",
     "avgpu_landscapes", "avgpu_set_landscape_chunk", "avgpu_last_landscape_ms",
     "avgpu_landscapes_indel", "avgpu_landscape_pairs",
 ]
@@ -502,6 +567,19 @@ def load_product(path=None):
     lib.avgpu_get_genotypes.restype = C.c_int
     lib.avgpu_get_genotypes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GENOTYPE_TOTALS)]
     lib.avgpu_last_genotypes_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    # the device-resident genotype arbiter (a diagnostic library may be an
+    # earlier build without it: tools/gpu/ab_var.sh measures such builds)
+    if p == LIB_PATH or hasattr(lib, "avgpu_classify_genotypes"):
+        lib.avgpu_classify_genotypes.restype = C.c_int
+        lib.avgpu_classify_genotypes.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
+        lib.avgpu_get_arbiter.restype = C.c_int
+        lib.avgpu_get_arbiter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        lib.avgpu_set_arbiter.restype = C.c_int
+        lib.avgpu_set_arbiter.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.avgpu_reset_arbiter.restype = C.c_int
+        lib.avgpu_reset_arbiter.argtypes = [C.c_void_p]
+        lib.avgpu_last_arbiter_ms.restype = C.c_int
+        lib.avgpu_last_arbiter_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     # mutational landscapes: the product only (the oracle runs avida_amd.landscape.spec)
     lib.avgpu_landscapes.restype = C.c_int
     lib.avgpu_landscapes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int,

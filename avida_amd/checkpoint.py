@@ -18,6 +18,10 @@ its own sites; avgpu_set_genotype_keys), `serial` / `spec` / `face` /
 `soup_perm` / `reaper` (the serial world's own state, avgpu_get_serial_state:
 its two streams' positions, speculative credits, connection-list rotations,
 BIRTH_METHOD 4's empty_cell_id_array and 5's reaper queue, rear first),
+`arb_rows` / `arb_summary` / `arb_sz_count` (the device-resident genotype
+arbiter's state where the world keeps one, avgpu_get_arbiter: raw
+avgpu_arbiter_row records, the raw avgpu_arbiter_summary and the name counters
+per genome size; restored through avgpu_set_arbiter, absent from older files),
 `version` and the byte sizes of the
 two raw structures (`state_size`, `stats_size`).  A file from before a
 structure grew (round 4 added births_cancelled and seed to the stats) loads
@@ -73,7 +77,18 @@ def save(lib, prefix, handle, ncells, nres, path):
     _call(lib, prefix, "get_serial_state", handle, C.byref(ser), spec.ctypes.data_as(C.c_void_p),
           face.ctypes.data_as(C.c_void_p), soup.ctypes.data_as(C.c_void_p), reaper.ctypes.data_as(C.c_void_p),
           len(reaper))
-    np.savez_compressed(path, states=np.frombuffer(st, dtype=np.uint8), tape=tape.astype(np.uint8), gkeys=gkeys,
+    extra = {}
+    if prefix == "avgpu_" and hasattr(lib, "avgpu_get_arbiter"):
+        # the device-resident genotype arbiter's state (a strip tile keeps none)
+        try:
+            rows, _, summary, sz = capi.get_arbiter(lib, handle)
+        except RuntimeError as e:
+            if "strip tiles" not in str(e):
+                raise
+        else:
+            extra = dict(arb_rows=rows.view(np.uint8), arb_summary=np.frombuffer(summary.tobytes(), dtype=np.uint8),
+                         arb_sz_count=sz)
+    np.savez_compressed(path, **extra, states=np.frombuffer(st, dtype=np.uint8), tape=tape.astype(np.uint8), gkeys=gkeys,
                         serial=np.frombuffer(ser, dtype=np.uint8), spec=spec, face=face, soup_perm=soup,
                         reaper=reaper[:max(0, ser.reaper_len)],
                         cap=np.int64(cap), stats=np.frombuffer(stats, dtype=np.uint8),
@@ -120,6 +135,10 @@ def load(lib, prefix, handle, path):
         arrs = [np.ascontiguousarray(z[k], dtype=t) for k, t in
                 (("spec", np.int32), ("face", np.uint8), ("soup_perm", np.int32), ("reaper", np.int32))]
         _call(lib, prefix, "set_serial_state", handle, C.byref(ser), *[a.ctypes.data_as(C.c_void_p) for a in arrs])
+    if "arb_rows" in z.files and prefix == "avgpu_" and hasattr(lib, "avgpu_set_arbiter"):
+        rows = np.frombuffer(z["arb_rows"].tobytes(), dtype=capi.ARBITER_ROW_DTYPE)
+        summary = np.frombuffer(z["arb_summary"].tobytes(), dtype=capi.ARBITER_SUMMARY_DTYPE)[0]
+        capi.set_arbiter(lib, handle, rows, summary, z["arb_sz_count"])
     stats = _struct(capi.AvgpuUpdateStats, z["stats"].tobytes(), "stats")
     _call(lib, prefix, "set_clock", handle, C.byref(stats))
     levels = np.ascontiguousarray(z["levels"], dtype=np.float64)

@@ -121,6 +121,16 @@ struct avgpu_world {
   hipEvent_t ev_gt[4] = {};
   double gt_ms = 0.0;
   int64_t gt_bytes = 0;
+  // the device-resident genotype arbiter (avgpu_classify_genotypes): buffers
+  // allocated at the first use, grown with the row buffer's policy; arb_n rows
+  // of state, arb_last the summary of the last classification (or set / reset)
+  ArbScratch arb = {};
+  bool arb_ready = false;
+  int64_t arb_n = 0;
+  avgpu_arbiter_summary arb_last = {};
+  hipEvent_t ev_arb[4] = {};
+  double arb_ms = 0.0;
+  int64_t arb_bytes = 0;
   // mutational landscapes (avgpu_landscapes): the scratch test world of
   // land_chunk cells the mutants run through and the per-chunk scratch (in its
   // allocs), created by the first call, re-created when land_chunk changes
@@ -720,6 +730,13 @@ int avgpu_destroy(avgpu_world* w) {
   for (double* p : w->srec_buf) if (p) hipFree(p);
   if (w->gt_rows) hipFree(w->gt_rows);
   for (hipEvent_t e : w->ev_gt) if (e) hipEventDestroy(e);
+  for (int k = 0; k < 2; k++) {
+    if (w->arb.row[k]) hipFree(w->arb.row[k]);
+    if (w->arb.key[k]) hipFree(w->arb.key[k]);
+  }
+  if (w->arb.table) hipFree(w->arb.table);
+  if (w->arb.h_sum) hipHostFree(w->arb.h_sum);
+  for (hipEvent_t e : w->ev_arb) if (e) hipEventDestroy(e);
   for (int i = 0; i < avgpu_world::RING; i++) {
     for (int k = 0; k <= NUM_CLASSES; k++)
       if (w->ring[i][k]) hipEventDestroy(w->ring[i][k]);
@@ -1380,6 +1397,237 @@ int avgpu_last_genotypes_ms(avgpu_world* w, double* device_ms, int64_t* bytes_co
   if (!w) return fail(AVGPU_EINVAL, "NULL world");
   if (device_ms) *device_ms = w->gt_ms;
   if (bytes_copied) *bytes_copied = w->gt_bytes;
+  return 0;
+}
+
+// ---- the device-resident genotype arbiter (arbiter.hip) ----
+static void arbiter_fresh_summary(avgpu_arbiter_summary* s) {
+  memset(s, 0, sizeof(*s));
+  s->next_id = 1;
+  s->dominant_row = -1;
+}
+
+// the fixed-size part: state, counters, name counters, the pinned summary
+static int arbiter_alloc(avgpu_world* w) {
+  if (w->arb_ready) return 0;
+  ArbScratch& A = w->arb;
+  int rc = w->alloc(&A.state, 1);
+  if (rc == 0) rc = w->alloc(&A.work, 1);
+  if (rc == 0) rc = w->alloc(&A.sz_count, AVGPU_MAX_GENOME + 1);
+  if (rc < 0) return rc;
+  if (hipHostMalloc((void**)&A.h_sum, sizeof(avgpu_arbiter_summary), hipHostMallocMapped | hipHostMallocCoherent) !=
+          hipSuccess ||
+      hipHostGetDevicePointer((void**)&A.d_sum, A.h_sum, 0) != hipSuccess)
+    return fail(AVGPU_ENOMEM, "pinned arbiter summary");
+  memset(A.h_sum, 0, sizeof(avgpu_arbiter_summary));
+  ArbState st = {1, 0, 0, 0ull};
+  COPY_SYNC(w, A.state, &st, sizeof(st), hipMemcpyHostToDevice);
+  for (hipEvent_t& e : w->ev_arb) HIPCHK(hipEventCreate(&e));
+  arbiter_fresh_summary(&w->arb_last);
+  w->arb_n = 0;
+  w->arb_ready = true;
+  return 0;
+}
+
+// room for `rows` rows (the stream is idle); keep: the current state survives
+static int arbiter_reserve(avgpu_world* w, int64_t rows, bool keep) {
+  ArbScratch& A = w->arb;
+  if (rows <= A.cap) return 0;
+  const int64_t want = std::min<int64_t>(std::max<int64_t>(w->W.n, 1), std::max<int64_t>(rows + rows / 4, 1024));
+  avgpu_arbiter_row* row[2] = {nullptr, nullptr};
+  uint64_t* key[2] = {nullptr, nullptr};
+  avgpu_genotype* table = nullptr;
+  hipError_t e = hipSuccess;
+  for (int k = 0; k < 2 && e == hipSuccess; k++) {
+    e = hipMalloc(&row[k], (size_t)want * sizeof(avgpu_arbiter_row));
+    if (e == hipSuccess) e = hipMalloc(&key[k], (size_t)want * sizeof(uint64_t));
+  }
+  if (e == hipSuccess) e = hipMalloc(&table, (size_t)want * sizeof(avgpu_genotype));
+  if (e == hipSuccess && keep && w->arb_n > 0) {
+    e = hipMemcpyAsync(row[A.cur], A.row[A.cur], (size_t)w->arb_n * sizeof(avgpu_arbiter_row),
+                       hipMemcpyDeviceToDevice, w->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(key[A.cur], A.key[A.cur], (size_t)w->arb_n * sizeof(uint64_t), hipMemcpyDeviceToDevice,
+                         w->stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(table, A.table, (size_t)w->arb_n * sizeof(avgpu_genotype), hipMemcpyDeviceToDevice,
+                         w->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(w->stream);
+  }
+  if (e != hipSuccess) {
+    for (int k = 0; k < 2; k++) { if (row[k]) hipFree(row[k]); if (key[k]) hipFree(key[k]); }
+    if (table) hipFree(table);
+    return fail(AVGPU_ENOMEM, std::string("arbiter rows: ") + hipGetErrorString(e));
+  }
+  for (int k = 0; k < 2; k++) {
+    if (A.row[k]) hipFree(A.row[k]);
+    if (A.key[k]) hipFree(A.key[k]);
+    A.row[k] = row[k];
+    A.key[k] = key[k];
+  }
+  if (A.table) hipFree(A.table);
+  A.table = table;
+  A.cap = want;
+  return 0;
+}
+
+int avgpu_classify_genotypes(avgpu_world* w, int64_t update, int32_t threshold, avgpu_arbiter_summary* out) {
+  if (!w || !out || threshold < 1)
+    return fail(AVGPU_EINVAL, "avgpu_classify_genotypes: NULL world, NULL out or threshold < 1");
+  if (w->W.tiled) return fail(AVGPU_EUNSUPPORTED, "genotype arbiter on strip tiles");
+  if (w->W.n >= (1ll << 31) - GT_SORT_TILE) return fail(AVGPU_EUNSUPPORTED, "genotype arbiter of 2^31 cells or more");
+  int rc = genotypes_alloc(w);
+  if (rc == 0) rc = arbiter_alloc(w);
+  if (rc < 0) return rc;
+  const GtScratch& S = w->gt;
+  ArbScratch& A = w->arb;
+  // the first part: the grouping; its totals are the summary's first fields
+  HIPCHK(hipMemsetAsync(S.totals, 0, sizeof(avgpu_genotype_totals), w->stream));
+  HIPCHK(hipEventRecord(w->ev_arb[0], w->stream));
+  launch_genotype_group(w->W, S, w->stream);
+  launch_arbiter_begin(A, S, update, w->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(w->ev_arb[1], w->stream));
+  HIPCHK(hipStreamSynchronize(w->stream));
+  const int64_t m = __atomic_load_n(&A.h_sum->num_genotypes, __ATOMIC_ACQUIRE);
+  if (m < 0 || m > S.n) return fail(AVGPU_ESTATE, "genotype arbiter: row count outside the world");
+  if (w->gt_rows_cap < m) {                     // the stream is idle
+    if (w->gt_rows) hipFree(w->gt_rows);
+    w->gt_rows = nullptr;
+    w->gt_rows_cap = 0;
+    const int64_t want = std::min<int64_t>(S.n, std::max<int64_t>(m + m / 4, 1024));
+    hipError_t e = hipMalloc(&w->gt_rows, (size_t)want * sizeof(avgpu_genotype));
+    if (e != hipSuccess) return fail(AVGPU_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    w->gt_rows_cap = want;
+  }
+  if ((rc = arbiter_reserve(w, std::max<int64_t>(m, 1), true)) < 0) return rc;
+  // every id of the new state is below next_id + m
+  int id_bits = 1;
+  while (id_bits < 50 && ((w->arb_last.next_id + m) >> id_bits) != 0) id_bits++;
+  if (((w->arb_last.next_id + m) >> id_bits) != 0) return fail(AVGPU_EUNSUPPORTED, "genotype ids of 2^50 or more");
+  HIPCHK(hipEventRecord(w->ev_arb[2], w->stream));
+  if (m > 0) {
+    launch_genotype_rows(w->W, S, w->gt_rows, w->stream);
+    HIPCHK(hipMemcpyAsync(A.table, w->gt_rows, (size_t)m * sizeof(avgpu_genotype), hipMemcpyDeviceToDevice,
+                          w->stream));
+  }
+  launch_arbiter_classify(A, S, A.table, m, w->arb_n, update, threshold, id_bits, w->stream);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipEventRecord(w->ev_arb[3], w->stream));
+  HIPCHK(hipStreamSynchronize(w->stream));
+  A.cur ^= 1;
+  w->arb_n = m;
+  memcpy(&w->arb_last, A.h_sum, sizeof(avgpu_arbiter_summary));
+  *out = w->arb_last;
+  float ms0 = 0.f, ms1 = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms0, w->ev_arb[0], w->ev_arb[1]));
+  HIPCHK(hipEventElapsedTime(&ms1, w->ev_arb[2], w->ev_arb[3]));
+  w->arb_ms = (double)ms0 + (double)ms1;
+  w->arb_bytes = sizeof(avgpu_arbiter_summary);
+  return 0;
+}
+
+int avgpu_get_arbiter(avgpu_world* w, avgpu_arbiter_row* rows, avgpu_genotype* table, int64_t cap,
+                      avgpu_arbiter_summary* summary, int64_t* sz_count) {
+  if (!w || cap < 0) return fail(AVGPU_EINVAL, "avgpu_get_arbiter: NULL world or negative cap");
+  if (w->W.tiled) return fail(AVGPU_EUNSUPPORTED, "genotype arbiter on strip tiles");
+  if (!w->arb_ready) {                          // never classified or set: a new world's state, nothing allocated
+    if (summary) arbiter_fresh_summary(summary);
+    if (sz_count) memset(sz_count, 0, (AVGPU_MAX_GENOME + 1) * sizeof(int64_t));
+    return 0;
+  }
+  const ArbScratch& A = w->arb;
+  const int64_t m = w->arb_n;
+  const bool want_rows = (rows || table) && cap > 0;
+  if (want_rows && cap < m)
+    return fail(AVGPU_EINVAL, "avgpu_get_arbiter: cap " + std::to_string(cap) + " rows, the arbiter has " +
+                                  std::to_string(m));
+  if (summary) *summary = w->arb_last;
+  if (sz_count)
+    HIPCHK(hipMemcpyAsync(sz_count, A.sz_count, (AVGPU_MAX_GENOME + 1) * sizeof(int64_t), hipMemcpyDeviceToHost,
+                          w->stream));
+  if (want_rows && m > 0) {
+    if (rows)
+      HIPCHK(hipMemcpyAsync(rows, A.row[A.cur], (size_t)m * sizeof(avgpu_arbiter_row), hipMemcpyDeviceToHost,
+                            w->stream));
+    if (table)
+      HIPCHK(hipMemcpyAsync(table, A.table, (size_t)m * sizeof(avgpu_genotype), hipMemcpyDeviceToHost, w->stream));
+  }
+  HIPCHK(hipStreamSynchronize(w->stream));
+  return want_rows ? (int)m : 0;
+}
+
+int avgpu_set_arbiter(avgpu_world* w, int64_t n, const avgpu_arbiter_row* rows,
+                      const avgpu_arbiter_summary* summary, const int64_t* sz_count) {
+  if (!w || n < 0 || (n > 0 && !rows) || !summary)
+    return fail(AVGPU_EINVAL, "avgpu_set_arbiter: NULL world, rows or summary, or negative n");
+  if (w->W.tiled) return fail(AVGPU_EUNSUPPORTED, "genotype arbiter on strip tiles");
+  if (n > w->W.n) return fail(AVGPU_EINVAL, "avgpu_set_arbiter: more rows than cells");
+  if (summary->next_id < 1) return fail(AVGPU_EINVAL, "avgpu_set_arbiter: next_id < 1");
+  for (int64_t j = 0; j < n; j++)
+    if (rows[j].genotype_key == 0 || (j > 0 && rows[j].genotype_key <= rows[j - 1].genotype_key))
+      return fail(AVGPU_EINVAL, "avgpu_set_arbiter: row " + std::to_string(j) +
+                                    ": keys must be non-zero and strictly ascending");
+  for (int64_t j = 0; j < n; j++) {
+    const avgpu_arbiter_row& r = rows[j];
+    if (r.genome_length < 0 || r.genome_length > AVGPU_MAX_GENOME || r.name_no < 0 || r.num_units < 0 ||
+        r.total_units < 0 || r.id < 1 || r.id >= summary->next_id)
+      return fail(AVGPU_EINVAL, "avgpu_set_arbiter: row " + std::to_string(j) +
+                                    ": genome_length outside 0..AVGPU_MAX_GENOME, a negative name_no, num_units "
+                                    "or total_units, or an id outside 1..next_id-1");
+  }
+  if (sz_count)
+    for (int q = 0; q <= AVGPU_MAX_GENOME; q++)
+      if (sz_count[q] < 0) return fail(AVGPU_EINVAL, "avgpu_set_arbiter: negative sz_count");
+  int rc = arbiter_alloc(w);
+  if (rc < 0) return rc;
+  HIPCHK(hipStreamSynchronize(w->stream));
+  if ((rc = arbiter_reserve(w, std::max<int64_t>(n, 1), false)) < 0) return rc;
+  ArbScratch& A = w->arb;
+  std::vector<uint64_t> keys((size_t)n);
+  int64_t dom = -1;
+  const uint64_t dom_key = summary->dominant_row >= 0 ? summary->dominant_state.genotype_key : 0ull;
+  int64_t thr = 0;
+  for (int64_t j = 0; j < n; j++) {
+    keys[j] = rows[j].genotype_key;
+    if (keys[j] == dom_key) dom = j;
+    thr += rows[j].threshold != 0;
+  }
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(A.row[A.cur], rows, (size_t)n * sizeof(avgpu_arbiter_row), hipMemcpyHostToDevice, w->stream));
+    HIPCHK(hipMemcpyAsync(A.key[A.cur], keys.data(), (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, w->stream));
+    HIPCHK(hipMemsetAsync(A.table, 0, (size_t)n * sizeof(avgpu_genotype), w->stream));
+  }
+  ArbState st = {summary->next_id, summary->tot_genotypes, summary->tot_threshold, dom >= 0 ? dom_key : 0ull};
+  HIPCHK(hipMemcpyAsync(A.state, &st, sizeof(st), hipMemcpyHostToDevice, w->stream));
+  if (sz_count)
+    HIPCHK(hipMemcpyAsync(A.sz_count, sz_count, (AVGPU_MAX_GENOME + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
+                          w->stream));
+  else
+    HIPCHK(hipMemsetAsync(A.sz_count, 0, (AVGPU_MAX_GENOME + 1) * sizeof(int64_t), w->stream));
+  HIPCHK(hipStreamSynchronize(w->stream));
+  w->arb_n = n;
+  w->arb_last = *summary;
+  w->arb_last.num_genotypes = n;
+  w->arb_last.num_threshold = thr;
+  w->arb_last.dominant_row = dom;
+  if (dom >= 0) w->arb_last.dominant_state = rows[dom];
+  else memset(&w->arb_last.dominant_state, 0, sizeof(avgpu_arbiter_row));
+  if (dom < 0) memset(&w->arb_last.dominant, 0, sizeof(avgpu_genotype));
+  return 0;
+}
+
+int avgpu_reset_arbiter(avgpu_world* w) {
+  if (!w) return fail(AVGPU_EINVAL, "NULL world");
+  avgpu_arbiter_summary s;
+  arbiter_fresh_summary(&s);
+  return avgpu_set_arbiter(w, 0, nullptr, &s, nullptr);
+}
+
+int avgpu_last_arbiter_ms(avgpu_world* w, double* device_ms, int64_t* bytes_copied) {
+  if (!w) return fail(AVGPU_EINVAL, "NULL world");
+  if (device_ms) *device_ms = w->arb_ms;
+  if (bytes_copied) *bytes_copied = w->arb_bytes;
   return 0;
 }
 

@@ -1005,6 +1005,46 @@ struct GtScratch {
 };
 void launch_genotype_group(const DevWorld& W, const GtScratch& S, hipStream_t s);
 void launch_genotype_rows(const DevWorld& W, const GtScratch& S, avgpu_genotype* d_out, hipStream_t s);
+// the stable LSD radix sort of the grouping over S.key[0][0 .. m), m <= S.n:
+// `passes` (even) 8-bit digits from bit 0; on completion S.key[0] holds the
+// keys ascending and S.cell[0][r] the position key r came from
+void launch_genotype_sort(const GtScratch& S, int64_t m, int passes, hipStream_t s);
+// the device-resident genotype arbiter (arbiter.hip).
+// ArbState: the world-level state; ArbWork: one classification's counters;
+// ArbScratch: the world's buffers, allocated at the first
+// avgpu_classify_genotypes / avgpu_set_arbiter -- 192 B per row of capacity
+// (two state rows of 48 B, two keys of 8 B, the table row of 80 B).
+static_assert(sizeof(avgpu_arbiter_row) == 48 && sizeof(avgpu_arbiter_summary) == 232, "arbiter rows");
+struct ArbState {
+  int64_t next_id, tot_genotypes, tot_threshold;
+  uint64_t best_key;        // the previous dominant (0: none)
+};
+struct ArbWork {
+  int32_t top, pad;         // the largest num_units
+  unsigned long long best_id;   // the lowest id among the rows at the top
+  unsigned long long num_new, num_matched, num_crossed, num_thr;
+  int64_t stay_row;         // the previous dominant's row where it stays, else -1
+  int64_t dom_row;
+};
+struct ArbScratch {
+  int64_t cap;              // rows of capacity
+  int cur;                  // which of row[] / key[] holds the state
+  avgpu_arbiter_row* row[2];    // [cap] (swapped per classification)
+  uint64_t* key[2];         // [cap] the rows' keys, dense (the match's binary search)
+  avgpu_genotype* table;    // [cap] the table rows of the last classification
+  ArbState* state;
+  ArbWork* work;
+  int64_t* sz_count;        // [AVGPU_MAX_GENOME + 1] names handed out per genome size
+  avgpu_arbiter_summary* h_sum;   // pinned, host-mapped
+  avgpu_arbiter_summary* d_sum;   // its device address
+};
+// the first part: after launch_genotype_group, the totals into the summary
+void launch_arbiter_begin(const ArbScratch& A, const GtScratch& S, int64_t update, hipStream_t s);
+// the rest: d_tab = the m table rows (launch_genotype_rows), n_prev the rows
+// of state in A.row[A.cur]; the new state goes to A.row[A.cur ^ 1].  id_bits:
+// every id of the new state is below 2^id_bits (<= 50).
+void launch_arbiter_classify(const ArbScratch& A, const GtScratch& S, const avgpu_genotype* d_tab, int64_t m,
+                             int64_t n_prev, int64_t update, int32_t threshold, int id_bits, hipStream_t s);
 // mutational landscapes (landscape.hip).  The mutants of every
 // base genome are numbered back to back: mutant m of the call is rank
 // m - mut_off[g] of genome g.  Ranks are cut into tiles of LAND_TILE aligned

@@ -382,6 +382,19 @@ void launch_genotype_group(const DevWorld& W, const GtScratch& S, hipStream_t s)
                                          S.totals);
 }
 
+// the same sort over the first m entries of key[0] (the arbiter's orderings,
+// arbiter.hip): the payload is the entry's position before the sort
+void launch_genotype_sort(const GtScratch& S, int64_t m, int passes, hipStream_t s) {
+  const int nblk = (int)((m + GT_SORT_TILE - 1) / GT_SORT_TILE);
+  for (int p = 0; p < passes; p++) {
+    const int a = p & 1, b = a ^ 1;
+    k_gt_hist<<<nblk, RS_THREADS, 0, s>>>(S.key[a], m, 8 * p, S.hist, nblk);
+    k_gt_scan<<<256, 64, 0, s>>>(S.hist, nblk, S.dtot);
+    k_gt_scatter<<<nblk, RS_THREADS, 0, s>>>(S.key[a], S.cell[a], S.key[b], S.cell[b], m, 8 * p, S.hist, nblk,
+                                             S.dtot, p == 0);
+  }
+}
+
 // after launch_genotype_group on the same stream: totals->num_genotypes rows into d_out
 void launch_genotype_rows(const DevWorld& W, const GtScratch& S, avgpu_genotype* d_out, hipStream_t s) {
   k_gt_tiles<true><<<(unsigned)S.ntile, GT_SEG_TILE, 0, s>>>(cells_of(W), S.key[0], S.cell[0], S.n, S.tile_agg,

@@ -13,8 +13,10 @@ Inject <org> [cell] [merit], InjectAll <org> [merit], InjectSequence <seq>
 [start] [end] [merit], LoadPopulation <file> [update] [cellid_offset] (.pop /
 .spop, avida_amd/population.py), SavePopulation [name] (<name>-<update>.spop),
 Print{Count,Average,Tasks,Time,Resource,Dominant}Data [file], SaveCheckpoint
-[file] / LoadCheckpoint <file> (full hardware state, avida_amd/checkpoint.py),
-Exit.  Other Print* events write nothing; anything else is an error.
+[file] / LoadCheckpoint <file> (full hardware state, avida_amd/checkpoint.py;
+after LoadCheckpoint the driver's update counter is the checkpoint's, so the
+next update processed is the one after it and later events fire by that
+numbering, as LoadPopulation's update argument does), Exit.  Other Print* events write nothing; anything else is an error.
 
     python -m avida_amd.driver -c <config dir> -d <data dir> [-u MAX_UPDATES]
 """
@@ -102,6 +104,16 @@ class ProductWorld:
         (avgpu_get_genotypes)"""
         return capi.get_genotypes(self.lib, self.h)
 
+    def classify_genotypes(self, update, threshold):
+        """one classification by the arbiter kept on the device
+        (avgpu_classify_genotypes): its summary record"""
+        return capi.classify_genotypes(self.lib, self.h, update, threshold)
+
+    def arbiter_state(self):
+        """(rows, table, summary, sz_count) of the last classification
+        (avgpu_get_arbiter)"""
+        return capi.get_arbiter(self.lib, self.h)
+
     def landscape(self, genomes, distance=1, chart=None):
         """the full substitution landscapes of `genomes` on the device
         (avgpu_landscapes): a list of landscape.Landscape"""
@@ -166,8 +178,10 @@ class Driver:
         # genotype classification runs every update when a data file needs it
         # (the reference's systematics manager classifies every birth)
         need = {"PrintCountData", "PrintDominantData", "SavePopulation", "PrintAverageData"}
-        self.arbiter = systematics.GenotypeArbiter(int(acfg.get("THRESHOLD", 3))) \
-            if any(e[2] in need for e in self.events) else None
+        # (on the device where the world keeps the arbiter there, else on the host)
+        kind = systematics.DeviceGenotypeArbiter if hasattr(self.world, "classify_genotypes") \
+            else systematics.GenotypeArbiter
+        self.arbiter = kind(int(acfg.get("THRESHOLD", 3))) if any(e[2] in need for e in self.events) else None
         self.rec.arbiter = self.arbiter
         self.done = False
         self.update = -1
@@ -177,8 +191,12 @@ class Driver:
 
     def _classify(self):
         """the arbiter takes the world's genotype table: the device's where
-        the world has one, else the census grouped on the host"""
+        the world has one, else the census grouped on the host; a world that
+        keeps the arbiter on the device classifies there"""
         w = self.world
+        if isinstance(self.arbiter, systematics.DeviceGenotypeArbiter):
+            self.arbiter.classify(w, max(self.update, 0))
+            return
         table, totals = w.genotypes() if hasattr(w, "genotypes") else systematics.table_from_census(w.census())
         self.arbiter.update_table(table, totals, max(self.update, 0))
 
@@ -235,7 +253,11 @@ class Driver:
             name = args[0] if args else f"checkpoint-{self.update}.npz"
             w.checkpoint(os.path.join(self.data_dir, name))
         elif action == "LoadCheckpoint":
-            self.rec.end_update(w.restore(os.path.join(self.config_dir, args[0])))
+            stats = w.restore(os.path.join(self.config_dir, args[0]))
+            self.rec.end_update(stats)
+            self.update = int(stats.update)          # the next update is the one after the checkpoint's
+            if isinstance(self.arbiter, systematics.DeviceGenotypeArbiter):
+                self.arbiter.attach(w)               # the checkpoint carried the arbiter's state
         elif action == "Exit":
             self.done = True
         elif action.startswith("Print"):

@@ -16,7 +16,10 @@ device call).  GenotypeArbiter.update_table classifies one table after each
 update; update(census) does the same from a census and also keeps every
 genotype's cells.  It is a batch restatement: births and deaths of one update are
 applied together, in cell order, because the batch world itself places and
-activates an update's offspring together.  Rules:
+activates an update's offspring together.
+DeviceGenotypeArbiter is the same arbiter kept on the device
+(avgpu_classify_genotypes): update_table is its specification,
+and only a summary returns per classification.  Rules:
 
 * a key not among the active genotypes becomes a new genotype; new ids are
   handed out in order of the first cell holding the key;
@@ -379,3 +382,177 @@ class GenotypeArbiter:
                 0, 0, 0, 0, maxfit, g.id, g.name]
 
 
+
+class GenotypeSnapshot:
+    """One active genotype of a DeviceGenotypeArbiter, as the classification
+    it was fetched from left it: plain values, not a live view.  After the
+    next classify() it still shows the old values; ask the arbiter again."""
+    __slots__ = ("_a", "_gen", "_j", "id", "key", "length", "update_born", "num_units", "total_units",
+                 "threshold", "name")
+
+    def __init__(self, arbiter, row, j):
+        self._a, self._gen, self._j = arbiter, arbiter._generation, j
+        self.key, self.id, self.length = int(row["genotype_key"]), int(row["id"]), int(row["genome_length"])
+        self.update_born, self.num_units = int(row["update_born"]), int(row["num_units"])
+        self.total_units, self.threshold = int(row["total_units"]), bool(row["threshold"])
+        k = int(row["name_no"])
+        self.name = "%03d-%s" % (self.length, name_letters(k - 1)) if k else "%03d-no_name" % self.length
+
+    @property
+    def cells(self):
+        a = self._a
+        if a._generation != self._gen or a.cell_order is None:
+            return None
+        j = self._j if self._j is not None else a._index(self.key)
+        return a.cell_order[a.cell_bounds[j]:a.cell_bounds[j + 1]]
+
+
+class _DeviceActive(_Active):
+    """key -> GenotypeSnapshot over the fetched state of a DeviceGenotypeArbiter"""
+
+    def __getitem__(self, key):
+        a = self._a
+        j = a._index(key)
+        if j < 0:
+            raise KeyError(key)
+        g = a._views.get(int(key))
+        if g is None:
+            g = a._views[int(key)] = GenotypeSnapshot(a, a.rows[j], j)
+        return g
+
+
+class DeviceGenotypeArbiter:
+    """The arbiter kept on the device (avgpu_classify_genotypes; DESIGN.md
+    10.5): classify() runs one classification there and keeps its summary.
+    The counts, the totals, the dominant and its data-file row come from the
+    summary alone.  Everything per genotype (keys, ids, ... table, active[...],
+    set_cells, genotype_averages of any genotype) is fetched lazily by one
+    avgpu_get_arbiter and cached until the next classify(), with the names
+    and meanings GenotypeArbiter gives them.
+
+    Genotype objects of this class (GenotypeSnapshot) are snapshots of the
+    classification they were fetched from; they do not follow the genotype
+    through later classifications as GenotypeArbiter's views do."""
+
+    census = None             # never fed a census
+
+    def __init__(self, threshold=3):
+        self.threshold = threshold
+        self.active = _DeviceActive(self)
+        self.world = None
+        self.summary = np.zeros(1, dtype=capi.ARBITER_SUMMARY_DTYPE)[0]
+        self.summary["next_id"], self.summary["dominant_row"] = 1, -1
+        self._generation = 0
+        self._drop()
+
+    def _drop(self):
+        self._generation += 1
+        self._state = None
+        self._views = {}
+        self._dominant = None
+        self.cell_order = self.cell_bounds = None
+
+    def classify(self, world, update):
+        """one classification of `world` (driver.ProductWorld) after `update`"""
+        self.world = world
+        self.summary = world.classify_genotypes(update, self.threshold)
+        self._drop()
+        return self.summary
+
+    def attach(self, world):
+        """take over the state `world` holds (after a restore)"""
+        self.world = world
+        self._drop()
+        self._state = world.arbiter_state()
+        self.summary = self._state[2]
+
+    # ---- from the summary alone ----
+    def num_genotypes(self):
+        return int(self.summary["num_genotypes"])
+
+    def num_threshold(self):
+        return int(self.summary["num_threshold"])
+
+    @property
+    def tot_genotypes(self):
+        return int(self.summary["tot_genotypes"])
+
+    @property
+    def tot_threshold(self):
+        return int(self.summary["tot_threshold"])
+
+    @property
+    def next_id(self):
+        return int(self.summary["next_id"])
+
+    @property
+    def best_key(self):
+        s = self.summary
+        return int(s["dominant_state"]["genotype_key"]) if s["dominant_row"] >= 0 else None
+
+    @property
+    def totals(self):
+        s = self.summary
+        return _totals(s["num_organisms"], s["num_genotypes"], s["sum_copied_size"], s["sum_executed_size"])
+
+    def dominant(self):
+        s = self.summary
+        if s["dominant_row"] < 0:
+            return None
+        if self._dominant is None:
+            self._dominant = GenotypeSnapshot(self, s["dominant_state"], int(s["dominant_row"]))
+        return self._dominant
+
+    @property
+    def best(self):
+        return self.dominant()
+
+    def genotype_averages(self, g):
+        s = self.summary
+        if s["dominant_row"] >= 0 and int(s["dominant_state"]["genotype_key"]) == g.key:
+            r = s["dominant"]
+        else:
+            r = self.table[self._index(g.key)]
+        n = int(r["num_gestated"])
+        if n == 0:
+            return 0.0, 0.0, 0.0, 0.0, 0.0, DBL_MIN
+        return (float(r["sum_merit"]) / n, int(r["sum_gestation"]) / n, float(r["sum_fitness"]) / n,
+                float(r["sum_repro_rate"]) / n, int(r["sum_copied"]) / n, float(r["max_fitness"]))
+
+    dominant_row = GenotypeArbiter.dominant_row
+
+    # ---- per genotype: one avgpu_get_arbiter, cached ----
+    def _fetch(self):
+        if self._state is None:
+            if self.world is None:
+                z = np.zeros(0, dtype=capi.ARBITER_ROW_DTYPE), np.zeros(0, dtype=capi.GENOTYPE_DTYPE)
+                self._state = (*z, self.summary, np.zeros(capi.MAX_GENOME + 1, dtype=np.int64))
+            else:
+                self._state = self.world.arbiter_state()
+        return self._state
+
+    @property
+    def rows(self):
+        return self._fetch()[0]
+
+    @property
+    def table(self):
+        return self._fetch()[1]
+
+    @property
+    def sz_count(self):
+        """genome size -> names handed out (the sizes with any)"""
+        sz = self._fetch()[3]
+        return {int(k): int(sz[k]) for k in np.flatnonzero(sz)}
+
+    keys = property(lambda self: self.rows["genotype_key"])
+    ids = property(lambda self: self.rows["id"])
+    lengths = property(lambda self: self.rows["genome_length"])
+    born = property(lambda self: self.rows["update_born"])
+    units = property(lambda self: self.rows["num_units"].astype(np.int64))
+    total = property(lambda self: self.rows["total_units"])
+    thr = property(lambda self: self.rows["threshold"] != 0)
+    name_no = property(lambda self: self.rows["name_no"].astype(np.int64))
+
+    _index = GenotypeArbiter._index
+    set_cells = GenotypeArbiter.set_cells

@@ -629,6 +629,77 @@ int avgpu_get_genotypes(avgpu_world* w, avgpu_genotype* out, int64_t cap,
  * device time of its kernels in ms (HIP events on the world's stream) and
  * the bytes it copied to the host. */
 int avgpu_last_genotypes_ms(avgpu_world* w, double* device_ms, int64_t* bytes_copied);
+
+/* ---- device-resident genotype arbiter ----
+ * The classification itself on the device: the state the reference's
+ * Systematics::GenotypeArbiter keeps per active genotype
+ * (systematics/GenotypeArbiter.cc:280-530: ClassifyNewUnit files a unit under
+ * its genotype, AdjustGenotype keeps abundances and the best genotype,
+ * nameGenotype names a genotype at the threshold, removeGenotype drops it with
+ * its last unit) lives beside the genotype table, and each classification
+ * returns one summary.  The rules are those of avida_amd/systematics.py
+ * (GenotypeArbiter.update_table), restated in DESIGN.md 10.5; every field is an
+ * integer or copied unchanged, so the two agree exactly. */
+typedef struct avgpu_arbiter_row {      /* 48 B, one per active genotype, keys ascending:   */
+  uint64_t genotype_key;                /* row j describes row j of the genotype table       */
+  int64_t id, update_born, total_units;
+  int32_t num_units, genome_length, name_no, threshold;
+} avgpu_arbiter_row;
+
+typedef struct avgpu_arbiter_summary {
+  int64_t update, num_organisms, num_genotypes, num_threshold;
+  int64_t tot_genotypes, tot_threshold, next_id;
+  int64_t num_new, num_gone, num_crossed;           /* of this classification */
+  int64_t sum_copied_size, sum_executed_size;       /* avgpu_genotype_totals' */
+  int64_t dominant_row;                             /* -1: no organisms */
+  avgpu_arbiter_row dominant_state;
+  avgpu_genotype dominant;                          /* its table row, byte for byte */
+} avgpu_arbiter_summary;
+
+/* One classification (ClassifyNewUnit, AdjustGenotype, nameGenotype and
+ * removeGenotype of every unit born or dead since the last one, applied
+ * together; systematics/GenotypeArbiter.cc:280-530): groups the living cells
+ * as avgpu_get_genotypes does and classifies the table against the resident
+ * state.  Stream-ordered behind the queued updates, complete on return; only
+ * the summary crosses to the host.  The world, its statistics and its random
+ * streams are untouched.  threshold < 1, out == NULL or w == NULL:
+ * AVGPU_EINVAL.  A strip tile or 2^31 cells or more: AVGPU_EUNSUPPORTED.
+ * The scratch (192 B per row on top of the table's) is allocated by the first
+ * call, grows with the row buffer and is kept. */
+int avgpu_classify_genotypes(avgpu_world* w, int64_t update, int32_t threshold, avgpu_arbiter_summary* out);
+/* The state of the last classification (or of avgpu_set_arbiter), without
+ * classifying again: what GenotypeArbiter::Begin's iterator walks
+ * (systematics/GenotypeArbiter.cc:280-530 keep it).  rows and table (either
+ * may be NULL) take one entry per active genotype, keys ascending; table holds
+ * the genotype table rows the classification was made from (zero after
+ * avgpu_set_arbiter until the next classification).  Returns the number of
+ * rows.  Both NULL or cap == 0: only summary / sz_count (either may be NULL)
+ * are filled, 0 is returned.  0 < cap < rows: AVGPU_EINVAL naming the count,
+ * the buffers untouched.  sz_count: AVGPU_MAX_GENOME + 1 counters, the names
+ * nameGenotype handed out per genome size.  A world that never classified
+ * reports a new world's state and allocates nothing. */
+int avgpu_get_arbiter(avgpu_world* w, avgpu_arbiter_row* rows, avgpu_genotype* table, int64_t cap,
+                      avgpu_arbiter_summary* summary, int64_t* sz_count);
+/* Installs a state (resume, or a hand-over from a host arbiter) in place of
+ * what ClassifyNewUnit / AdjustGenotype / nameGenotype / removeGenotype built
+ * (systematics/GenotypeArbiter.cc:280-530).  Rows must have strictly ascending
+ * non-zero keys, genome_length in 0 .. AVGPU_MAX_GENOME, non-negative name_no,
+ * num_units and total_units and ids in 1 .. summary->next_id - 1, and n must
+ * not exceed the world's cells, else AVGPU_EINVAL with the device state
+ * unchanged.  summary supplies next_id, tot_genotypes,
+ * tot_threshold and the dominant's key (dominant_state.genotype_key when
+ * dominant_row >= 0); sz_count NULL: all zero. */
+int avgpu_set_arbiter(avgpu_world* w, int64_t n, const avgpu_arbiter_row* rows,
+                      const avgpu_arbiter_summary* summary, const int64_t* sz_count);
+/* The state of a new world: no active genotype, next_id 1, no name handed out
+ * (a fresh Systematics::GenotypeArbiter, systematics/GenotypeArbiter.cc:280-530). */
+int avgpu_reset_arbiter(avgpu_world* w);
+/* Timing of the last avgpu_classify_genotypes (no reference equivalent; the
+ * work of systematics/GenotypeArbiter.cc:280-530 per update): the device time
+ * of its kernels in ms (HIP events on the world's stream) and the bytes that
+ * crossed to the host. */
+int avgpu_last_arbiter_ms(avgpu_world* w, double* device_ms, int64_t* bytes_copied);
+
 /* Verification (no reference equivalent): one 64-bit digest per cell of
  * cells first .. first+count-1 into host memory -- a chained mix over the 32-bit
  * words of the cell's state record, as avgpu_get_states returns it, and its

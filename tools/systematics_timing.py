@@ -8,8 +8,16 @@ update, the script times what the driver does for the genotype data files:
   (wall), the device time of its kernels (HIP events on the world's stream,
   avgpu_last_genotypes_ms), the bytes copied to the host, and
   GenotypeArbiter.update_table (wall);
+* a build with the device arbiter (avgpu_classify_genotypes) too: in the same
+  session, on the same world, right after the route above at every update,
+  DeviceGenotypeArbiter.classify (wall), the device time of its kernels
+  (avgpu_last_arbiter_ms) and the bytes that crossed to the host; the two
+  arbiters are compared at the end;
 * a build without it (--root <checkout of an earlier commit>): get_census
   (wall, 48 B per cell) and GenotypeArbiter.update (wall).
+
+With --table FILE the per-update means of the routes are also written as a
+text table (device ms, bytes to the host, wall ms of the systematics step).
 
 The update itself is timed the same way (queued run_update + sync, wall).
 
@@ -31,6 +39,7 @@ def main():
     ap.add_argument("--side", type=int, default=1024)
     ap.add_argument("--burn-in", type=int, default=None)
     ap.add_argument("--seed", type=int, default=101)
+    ap.add_argument("--table", default=None, help="write the routes' means as a text table to this file")
     a = ap.parse_args()
     root = os.path.abspath(a.root)
     sys.path.insert(0, root)
@@ -48,6 +57,12 @@ def main():
     capi.check(lib, lib.avgpu_sync(h))
     table_path = hasattr(capi, "get_genotypes")
     arb = systematics.GenotypeArbiter()
+    device_path = table_path and hasattr(lib, "avgpu_classify_genotypes")
+    if device_path:
+        class World:                              # what DeviceGenotypeArbiter asks of a world
+            classify_genotypes = staticmethod(lambda update, thr: capi.classify_genotypes(lib, h, update, thr))
+            arbiter_state = staticmethod(lambda: capi.get_arbiter(lib, h))
+        darb = systematics.DeviceGenotypeArbiter(arb.threshold)
     rows = []
     for u in range(a.updates + 1):            # row 0 (every genotype is new; scratch allocated) is reported apart
         t0 = time.perf_counter()
@@ -73,6 +88,16 @@ def main():
                      bytes_to_host=census.nbytes, get_census_ms=1e3 * (t2 - t1), arbiter_update_ms=1e3 * (t3 - t2))
         r["systematics_ms"] = 1e3 * (t3 - t1)
         r["dominant"] = [arb.dominant().id, arb.dominant().num_units, arb.num_threshold()]
+        if device_path:
+            t4 = time.perf_counter()
+            darb.classify(World, burn + u)
+            t5 = time.perf_counter()
+            ms, nbytes = C.c_double(), C.c_int64()
+            capi.check(lib, lib.avgpu_last_arbiter_ms(h, C.byref(ms), C.byref(nbytes)))
+            r.update(classify_device_ms=ms.value, classify_bytes_to_host=nbytes.value,
+                     classify_systematics_ms=1e3 * (t5 - t4))
+            g = darb.dominant()
+            assert r["dominant"] == [g.id, g.num_units, darb.num_threshold()], (r["dominant"], g.id)
         rows.append(r)
         print(json.dumps(r), flush=True)
     steady = rows[1:]
@@ -95,7 +120,58 @@ def main():
             exact = exact and bool((dev <= bound).all())
             worst = max(worst, float((dev / np.maximum(ref[f], 1e-300)).max()))
         out["check"] = {"table_equals_census_table": exact, "max_relative_sum_deviation": worst}
+    if device_path:
+        import numpy as np
+        same = all(np.array_equal(getattr(darb, f), getattr(arb, f))
+                   for f in ("keys", "ids", "lengths", "born", "units", "total", "thr", "name_no"))
+        same = same and (darb.next_id, darb.tot_genotypes, darb.tot_threshold, darb.sz_count, darb.best_key) == \
+            (arb.next_id, arb.tot_genotypes, arb.tot_threshold, arb.sz_count, arb.best_key)
+        m = out["mean"]
+        out.setdefault("check", {})["device_arbiter_equals_host_arbiter"] = bool(same)
+        out["ratio_systematics_ms"] = m["systematics_ms"] / m["classify_systematics_ms"]
     print(json.dumps(out), flush=True)
+    if a.table:
+        m = out["mean"]
+        lines = ["# tools/systematics_timing.py --side %d: per-update means over the %d updates after %d burn-in updates,"
+                 % (a.side, len(steady), burn),
+                 "# %d cells, %.0f organisms, %.0f genotypes; update itself %.3f ms (wall)"
+                 % (n, m["organisms"], m["genotypes"], m["update_ms"]),
+                 "%-44s %12s %16s %16s" % ("route", "device ms", "bytes to host", "systematics ms")]
+        if table_path:
+            lines.append("%-44s %12.3f %16.0f %16.3f" % ("get_genotypes + GenotypeArbiter.update_table",
+                                                        m["device_ms"], m["bytes_to_host"], m["systematics_ms"]))
+        else:
+            lines.append("%-44s %12s %16.0f %16.3f" % ("get_census + GenotypeArbiter.update", "-",
+                                                      m["bytes_to_host"], m["systematics_ms"]))
+        if device_path:
+            lines.append("%-44s %12.3f %16.0f %16.3f" % ("classify_genotypes (device arbiter)",
+                                                        m["classify_device_ms"], m["classify_bytes_to_host"],
+                                                        m["classify_systematics_ms"]))
+            lines.append("# ratio of the systematics step, host route / device route: %.1f"
+                         % out["ratio_systematics_ms"])
+            lines.append("# the two arbiters agree at the end: %s" % out["check"]["device_arbiter_equals_host_arbiter"])
+            import statistics
+            mh = statistics.median(x["systematics_ms"] for x in steady)
+            md = statistics.median(x["classify_systematics_ms"] for x in steady)
+            lines.append("# medians over the same %d updates: host route %.3f ms, device route %.3f ms (ratio %.1f)"
+                         % (len(steady), mh, md, mh / md))
+            slow = [x for x in steady if x["classify_systematics_ms"] > 3.0 * md]
+            if slow:
+                lines.append("# device route, wall time above 3 x its median (in the mean above): "
+                             + ", ".join("update %d %.1f ms (device %.3f ms)"
+                                         % (x["update"], x["classify_systematics_ms"], x["classify_device_ms"])
+                                         for x in slow))
+            lines.append("# first classification (update %d: every genotype new, buffers allocated): host route %.1f ms, "
+                         "device route %.3f ms wall, %.3f ms device"
+                         % (rows[0]["update"], rows[0]["systematics_ms"], rows[0]["classify_systematics_ms"],
+                            rows[0]["classify_device_ms"]))
+            lines.append("#")
+            lines.append("# per update: update, device ms and wall ms of classify_genotypes, wall ms of the host route, "
+                         "wall ms of the update")
+            lines += ["%d %.3f %.3f %.2f %.3f" % (x["update"], x["classify_device_ms"], x["classify_systematics_ms"],
+                                                  x["systematics_ms"], x["update_ms"]) for x in rows]
+        with open(a.table, "w") as f:
+            f.write("\n".join(lines) + "\n")
     lib.avgpu_destroy(h)
 
 
