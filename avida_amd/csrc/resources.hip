@@ -190,7 +190,11 @@ __device__ __forceinline__ double res_source_sink(const ResParam& P, double a_c,
 // (k = 3..6: E, SE, S, SW), added in increasing (computing cell, k) order of
 // global cell ids like the reference's loop over i (an 8-entry sorting
 // network keeps the order in registers); a pointer the geometry lacks adds
-// nothing (cSpatialResCount::SetPointers)
+// nothing (cSpatialResCount::SetPointers).  A pointer that leads back to c
+// itself (E on a torus one column wide, S on one a row high) is both c's own
+// and an incoming one under the same (cell, k): FlowMatter subtracts from
+// elem1 before it adds to elem2, so the key's low bit puts own before
+// incoming -- the network is not stable and must never see a tie
 __device__ __forceinline__ double res_edge_sum(const ResParam& P, int X, int Y, int x, int y, const double (&own)[4],
                                                const double (&in)[4], double d) {
   const int64_t gc = (int64_t)y * X + x;
@@ -200,7 +204,7 @@ __device__ __forceinline__ double res_edge_sum(const ResParam& P, int X, int Y, 
   for (int k = 3; k <= 6; k++) {                     // own pointers: slots 0..3
     int nx, ny;
     const bool ok = res_ptr(P.geometry, X, Y, x, y, k, nx, ny);
-    key[k - 3] = ok ? gc * 8 + k : INT64_MAX;
+    key[k - 3] = ok ? (gc * 8 + k) * 2 : INT64_MAX;
     val[k - 3] = ok ? -own[k - 3] : 0.0;
   }
 #pragma unroll
@@ -209,7 +213,7 @@ __device__ __forceinline__ double res_edge_sum(const ResParam& P, int X, int Y, 
     const int jx = wrap1(x - dx, X), jy = wrap1(y - dy, Y);
     int nx, ny;
     const bool ok = res_ptr(P.geometry, X, Y, jx, jy, k, nx, ny) && nx == x && ny == y;
-    key[k + 1] = ok ? ((int64_t)jy * X + jx) * 8 + k : INT64_MAX;
+    key[k + 1] = ok ? (((int64_t)jy * X + jx) * 8 + k) * 2 + 1 : INT64_MAX;
     val[k + 1] = ok ? in[k - 3] : 0.0;
   }
   // Batcher odd-even merge sort of 8 (19 compare-exchanges)

@@ -16,6 +16,7 @@ import pytest
 
 from avida_amd import capi, files
 import test_checkpoint as tc
+from res_util import set_resources
 
 
 def _queue(b, n):
@@ -27,19 +28,12 @@ def _queue(b, n):
             assert rc == 0, b.lib.avgpu_last_error().decode()
 
 
-def _set_resources(b, levels, grids):
-    n = b.ncells
-    lv = (C.c_double * max(1, len(levels)))(*levels)
-    sp = (C.c_double * max(1, len(grids) * n))(*[v for g in grids for v in g])
-    b._call("set_resources", b.h, lv, sp)
-
-
 def _sequence(b, golden):
     _queue(b, 3)
     for c in (5, 17, 200, 513):
         b.kill(c)                                  # read-modify-write of the cell's control word
     levels, grids = b.resources(spatial=True)
-    _set_resources(b, [0.5 * v for v in levels], [[0.5 * v for v in g] for g in grids])
+    set_resources(b, [0.5 * v for v in levels], [[0.5 * v for v in g] for g in grids])
     _queue(b, 2)
     anc = files.read_org(os.path.join(golden, "default-heads.org"), b.instset)
     tests = b.test_genomes([anc, anc[:40] + anc[41:]])   # the test CPU's own world, its tables copied

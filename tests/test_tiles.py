@@ -12,6 +12,7 @@ import torch.multiprocessing as mp
 from avida_amd import capi, tiles
 import parity_util as pu
 import tile_util as tu
+from res_util import bits
 
 CAP = 512
 
@@ -109,9 +110,9 @@ def resource_grids_match(single_res, tile_bs, T, X, Y):
         tl, tg = b.resources(spatial=True)
         for r in range(len(lv)):
             if any(grids[r]):
-                assert tg[r] == grids[r][k * per:(k + 1) * per], (k, r)
+                assert bits(tg[r]) == bits(grids[r][k * per:(k + 1) * per]), (k, r)
             else:
-                assert tl[r] == lv[r], (k, r, tl[r], lv[r])
+                assert bits([tl[r]]) == bits([lv[r]]), (k, r, tl[r], lv[r])
 
 
 @pytest.mark.parametrize("T,geometry", [(2, 2), (4, 2), (4, 1)])

@@ -50,8 +50,10 @@ def setup(golden, X, Y, seed=7, geometry=2, overrides=None, env=None):
     return iset, env, cfg, genomes
 
 
-def make_tile(kind, golden, X, Y, T, k, seed=7, geometry=2, device="cpu", overrides=None, arena=0, env=None):
-    """Backend + Tile for strip k of T (rows [k*Y/T, (k+1)*Y/T))."""
+def make_tile(kind, golden, X, Y, T, k, seed=7, geometry=2, device="cpu", overrides=None, arena=0, env=None,
+              empty=False):
+    """Backend + Tile for strip k of T (rows [k*Y/T, (k+1)*Y/T)); empty: no
+    organisms (the directed resource tests)."""
     iset, env, cfg, genomes = setup(golden, X, Y, seed, geometry, overrides, env)
     rows = Y // T
     b = ol.Backend(kind, cfg, iset, env, ncells=rows * X)
@@ -59,7 +61,8 @@ def make_tile(kind, golden, X, Y, T, k, seed=7, geometry=2, device="cpu", overri
         import torch
         b.lib.avgpu_set_stream(b.h, C_void(torch.cuda.current_stream().cuda_stream))
     t = tiles.Tile(b.lib, b.p, b.h, k * rows, T, device, arena)
-    b.set_orgs(0, genomes[k * rows * X:(k + 1) * rows * X], deterministic=False)
+    if not empty:
+        b.set_orgs(0, genomes[k * rows * X:(k + 1) * rows * X], deterministic=False)
     return b, t
 
 
