@@ -38,6 +38,41 @@ __device__ __forceinline__ int neighbours(const DevWorld& W, int cell, int* out)
     }
   return n;
 }
+// The same neighbours at fixed slots: out[k] is neighbour k of the order above
+// when bit k of the returned mask is set; a slot a bounded geometry leaves out
+// holds the cell itself (an address that is safe to load).  The valid slots in
+// ascending k are neighbours()' list, so a caller can load all eight cells'
+// state in one batch and build its candidate list from registers.
+__device__ __forceinline__ uint32_t neighbours_mask(const DevWorld& W, int cell, int (&out)[8]) {
+  const int X = W.world_x, R = W.rows;
+  const int x = cell % X, y = cell / X;
+  const bool bounded = W.geometry == 1;
+  uint32_t mask = 0;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    const int j = k < 4 ? k : k + 1;           // skip the centre
+    const int dx = j % 3 - 1, dy = j / 3 - 1;
+    int nx = x + dx, ny = y + dy;
+    bool ok = true;
+    if (bounded) ok = nx >= 0 && nx < X;
+    else nx = nx < 0 ? nx + X : (nx >= X ? nx - X : nx);
+    int c;
+    if (ny >= 0 && ny < R) {
+      c = ny * X + nx;
+    } else if (!W.tiled) {
+      if (bounded) ok = false;
+      ny = ny < 0 ? ny + R : ny - R;
+      c = ny * X + nx;
+    } else {
+      const int gy = W.row0 + ny;
+      if (bounded && (gy < 0 || gy >= W.global_rows)) ok = false;
+      c = (int)W.n + (ny < 0 ? 0 : X) + nx;
+    }
+    out[k] = ok ? c : cell;
+    mask |= (ok ? 1u : 0u) << k;
+  }
+  return mask;
+}
 
 // Divide_DoMutations' edits (cpu/cHardwareBase.cc:296-569), drawn in the
 // interpreter in the reference's order and stored with the birth record
@@ -175,7 +210,7 @@ __device__ __forceinline__ void apply_edits_wave(const DevWorld& W, int64_t r, u
   int e[5];
 #pragma unroll
   for (int k = 0; k < 5; k++) e[k] = W.b_edit[(int64_t)k * W.rcap + r];
-  apply_edits_core(W, r, e, W.b_len0[r], W.b_len[r], child);
+  apply_edits_core(W, r, e, W.b_len0[r], W.b_inh[r * BI_WORDS + BI_LEN], child);
 }
 
 // ActivateOrganism (main/cPopulation.cc:1320-1340) + SetupOffspring
@@ -268,10 +303,12 @@ __device__ __forceinline__ void child_quad(uint4 v, int k, int len, uint4* __res
   d4[k] = make_uint4(x[0], x[1], x[2], x[3]);
 }
 // PRE: the genome's first PRE quads are already in registers (pre), loaded by
-// the caller before it knew whether the record won its cell
+// the caller before it knew whether the record won its cell; lt: the parent's
+// last task counts, in registers too (the caller loaded them with the row)
 template <int PRE = 0>
 __device__ __forceinline__ void setup_child_lane(const DevWorld& W, int64_t c, const Child& b,
-                                                 const uint8_t* __restrict__ src, const uint4* pre = nullptr) {
+                                                 const uint8_t* __restrict__ src, const uint4* pre,
+                                                 const int (&lt)[12]) {
   const int64_t N = W.n;
   const int len = b.len;
   const uint4* __restrict__ s4 = reinterpret_cast<const uint4*>(src);
@@ -316,22 +353,28 @@ __device__ __forceinline__ void setup_child_lane(const DevWorld& W, int64_t c, c
   if (W.rec_off) W.rec_off[c] = -1;             // offspring: counter streams
 #pragma unroll
   for (int q = 0; q < AVGPU_NUM_LOGIC_TASKS; q++)   // last_task_count = the parent's (:447)
-    W.last_task[(int64_t)q * N + c] = b.ltask[(int64_t)q * b.lstride];
+    W.last_task[(int64_t)q * N + c] = lt[q];
 }
 
 // the phenotype record r hands its offspring
-__device__ __forceinline__ Child child_of_record(const DevWorld& W, int64_t i) {
+// (q0..q2: the row's first three quads, q6: its BI_PARENT quad, in registers)
+__device__ __forceinline__ Child child_of_row(const DevWorld& W, int64_t i, int4 q0, int4 q1, int4 q2, int4 q6) {
   Child b;
-  const int4* row = reinterpret_cast<const int4*>(W.b_inh + i * BI_WORDS);
-  const int4 q0 = row[0], q1 = row[1], q2 = row[2];       // 16-B loads of the record's row
-  static_assert(BI_MERIT == 0 && BI_GEN == 4 && BI_RLO == 8 && BI_LTASK == 12, "b_inh row layout");
-  b.len = W.b_len[i];
+  static_assert(BI_MERIT == 0 && BI_FITNESS == 2 && BI_GEN == 4 && BI_CCOPIED == 5 && BI_EXEC == 6 && BI_GEST == 7 &&
+                BI_RLO == 8 && BI_RHI == 9 && BI_RCTR == 10 && BI_FINAL == 11 && BI_LTASK == 12 &&
+                BI_PARENT == 24 && BI_LEN == 26, "b_inh row layout");
+  b.len = q6.z;
   b.merit = __hiloint2double(q0.y, q0.x); b.fitness = __hiloint2double(q0.w, q0.z);
   b.gen = q1.x; b.ccopied = q1.y; b.exec = q1.z; b.gest = q1.w;
   b.lo = (uint32_t)q2.x; b.hi = (uint32_t)q2.y; b.ctr = (uint32_t)q2.z;
   b.hs = 0x10000u - BI_TIME(q2.w);
   b.ltask = W.b_inh + i * BI_WORDS + BI_LTASK; b.lstride = 1;
   return b;
+}
+__device__ __forceinline__ Child child_of_record(const DevWorld& W, int64_t i) {
+  const int4* row = reinterpret_cast<const int4*>(W.b_inh + i * BI_WORDS);
+  const int4 q0 = row[0], q1 = row[1], q2 = row[2], q6 = row[BI_PARENT / 4];   // 16-B loads of the record's row
+  return child_of_row(W, i, q0, q1, q2, q6);
 }
 
 }  // namespace

@@ -175,7 +175,7 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   // offspring of one slice (device.h); test worlds never enqueue births
   W.rcap = n + (test_buffers ? 16 : std::max<int64_t>(4096, n / 4));
   const int64_t R = W.rcap;
-  A(b_count, BQ_WORDS); A(b_list, n); A(b_parent, R); A(b_seq, R); A(b_len, R); A(b_len0, R); A(b_edit, 5 * R);
+  A(b_count, BQ_WORDS); A(b_list, n); A(b_len0, R); A(b_edit, 5 * R);
   // DIV_MUT_PROB arena: three times the largest expected substitutions per
   // record plus 16 (offsets are int32); a fill past it is counted
   // (AVGPU_CNT_SUB_OVERFLOW), never written
@@ -214,8 +214,7 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   W.seg_any = (pois || site) ? 1 : 0;
   W.pois_any = pois ? 1 : 0;
   for (int q = 0; q < 5; q++) W.pois_L[q] = pmeans[q] > 0.0 ? std::exp(-pmeans[q]) : 0.0;
-  A(b_inh, (size_t)BI_WORDS * R); A(b_target, R); A(b_state, R);
-  A(b_prio, R); A(b_genome, (size_t)R * TAPE_SLOT);
+  A(b_inh, (size_t)BI_WORDS * R); A(b_genome, (size_t)R * TAPE_SLOT);
   // placement scratch with two ghost rows (strip tiles)
   // occupancy, owners and the four placement rounds' claims, each with the two
   // ghost rows a strip tile keeps after its n cells

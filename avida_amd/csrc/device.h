@@ -19,12 +19,19 @@
 #define TAPE_SLOT 2048
 // birth record row b_inh[r * BI_WORDS ..]: merit, fitness (doubles), generation,
 // copied size, executed size, gestation time, the offspring's RNG key and
-// counter, the parent's last task counts
+// counter, the parent's last task counts; then the record's placement state
+// (words 24..31: its parent's cell, the parent's divide number, the offspring's
+// length after the divide mutations, its BS_* state (world.hip), its target of
+// the current round and that round's claim key, 8-B aligned) -- everything a
+// placement kernel needs of a record is in the row it loads first
 // (BI_FINAL bit 0 = 1: the divide left the offspring's fitness and key and the
 // parent's phenotype to finalize_key / finalize_phenotype, world.hip; bits
 // 16..31 the offspring's birth time in the update, 1/2^16 -- DESIGN.md 5)
 enum { BI_MERIT = 0, BI_FITNESS = 2, BI_GEN = 4, BI_CCOPIED = 5, BI_EXEC = 6, BI_GEST = 7,
-       BI_RLO = 8, BI_RHI = 9, BI_RCTR = 10, BI_FINAL = 11, BI_LTASK = 12, BI_WORDS = 32 };
+       BI_RLO = 8, BI_RHI = 9, BI_RCTR = 10, BI_FINAL = 11, BI_LTASK = 12,
+       BI_PARENT = 24, BI_SEQ = 25, BI_LEN = 26, BI_STATE = 27, BI_TARGET = 28, BI_PRIO = 30, BI_WORDS = 32 };
+static_assert(BI_LTASK + 12 <= BI_PARENT && BI_PARENT % 4 == 0 && BI_TARGET % 4 == 0 && BI_PRIO % 2 == 0 &&
+              BI_PRIO + 2 == BI_WORDS, "b_inh row: the placement words are its last two quads");
 #define BI_TIME(w) ((uint32_t)(w) >> 16)
 #define CODE_MASK 0x3F
 #define TF_COPIED 0x40
@@ -151,10 +158,7 @@ struct DevWorld {
   int64_t rcap;       // n + ocap
   int32_t* b_count;   // [BQ_WORDS] (BQ_* below)
   int32_t* b_list;    // [n] primary record ids, appended per wave after the loop
-  int32_t* b_parent;  // [rcap]
-  uint32_t* b_seq;    // [rcap]
-  int32_t* b_len;     // [rcap]  offspring length after the divide mutations
-  int32_t* b_len0;    // [rcap]  the child's length before them (b_genome holds that child)
+  int32_t* b_len0;    // [rcap]  the child's length before the divide mutations (b_genome holds that child)
   int32_t* b_edit;    // [5][rcap] its divide-mutation edits (interp.hip edit_word; 0 = none)
   // variable-count divide-mutation edits of record r (only read when
   // seg_any): segment k holds b_pcnt[k][r] edit words from
@@ -165,14 +169,13 @@ struct DevWorld {
   int32_t* b_pofs;    // [NSEG][rcap]
   int32_t* b_pcnt;    // [NSEG][rcap]
   // what the offspring of record r inherits (cPhenotype::SetupOffspring,
-  // main/cPhenotype.cc:349-447), one 128-B row per record (BI_* below):
-  // written with 16-B stores at the divide, read with 16-B loads at
-  // activation -- as [field][rcap] rows every field was a scattered 4-B
-  // access whose line held no other field of the record
+  // main/cPhenotype.cc:349-447) and the record's placement state (parent,
+  // divide number, length, BS_* state, target, claim key), one 128-B row per
+  // record (BI_* above): written with 16-B stores at the divide, read with
+  // 16-B loads by placement and activation -- as [field][rcap] rows every
+  // field was a scattered 4-B access whose line held no other field of the
+  // record (primary records sit at their parent's cell id: ~6 % of the rows)
   int32_t* b_inh;     // [rcap][BI_WORDS]
-  int32_t* b_target;  // [rcap]
-  int8_t* b_state;    // [rcap]  BS_* (world.hip)
-  unsigned long long* b_prio; // [rcap] claim key of the record's current round (world.hip claim_key)
   uint8_t* b_genome;  // [rcap][TAPE_SLOT]
   // placement scratch, n cells + 2 ghost rows (strip tiles, below)
   uint8_t* occ;       // [n + 2X]
@@ -343,7 +346,7 @@ struct DevWorld {
   const double* totals;   // the step's totals (k_block_counts; TOT_* below)
 };
 // (the interpreter loads the fields by scalar offset: none may move)
-static_assert(sizeof(DevWorld) == 1664, "DevWorld's size");
+static_assert(sizeof(DevWorld) == 1616, "DevWorld's size");
 
 // ---------------------------------------------------------------------------
 // The scratch vectors the update's kernels and the host hand each other.  Each
@@ -405,7 +408,9 @@ enum {
   BQ_PRIMARY = 0,    // primary records listed in b_list
   BQ_OVERFLOW = 1,   // overflow records used
   BQ_SUBS = 2,       // b_subs entries used
-  BQ_WORDS = 3
+  BQ_PICKED = 3,     // + m: the records that picked in placement round m = 1..3 of a single
+                     // world (k_place_round counts them; 0: the next launch has nothing pending)
+  BQ_WORDS = 7
 };
 // Rows of class_list / class_count: LIST_NEWBORN the newborn pass's class-0
 // organisms (k_activate), k = 1..3 the organisms k_allot put in class k,

@@ -1796,20 +1796,11 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
                 uint32_t clo = 0u, chi = 0u;
                 if (!defer) derive_key(olo, ohi, (uint32_t)nd, 0x1B873593U, clo, chi);
                 // the record arrays, loaded together (see OPQ above)
-                int32_t* b_parent = W.b_parent;
-                uint32_t* b_seq = W.b_seq;
-                int32_t* b_len = W.b_len;
                 int32_t* b_len0 = W.b_len0;
                 int32_t* b_edit = W.b_edit;
-                int8_t* b_state = W.b_state;
-                int32_t* b_target = W.b_target;
                 int32_t* b_inh = W.b_inh;
                 int64_t rcap = W.rcap;
-                OPQ(b_parent); OPQ(b_seq); OPQ(b_len); OPQ(b_len0); OPQ(b_edit);
-                OPQ(b_state); OPQ(b_target); OPQ(b_inh); OPQ(rcap);
-                st_async_u32(b_parent + rec, (uint32_t)cell);
-                st_async_u32(b_seq + rec, (uint32_t)nd);
-                st_async_u32(b_len + rec, (uint32_t)len);
+                OPQ(b_len0); OPQ(b_edit); OPQ(b_inh); OPQ(rcap);
                 st_async_u32(b_len0 + rec, (uint32_t)child);   // the placement launch edits the copy
                 st_async_u32(b_edit + rec, (uint32_t)e0);
                 st_async_u32(b_edit + rcap + rec, (uint32_t)e1);
@@ -1838,8 +1829,12 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
                 st_async_b128(irow + 12, (uint32_t)tc[0], (uint32_t)tc[1], (uint32_t)tc[2], (uint32_t)tc[3]);
                 st_async_b128(irow + 16, (uint32_t)tc[4], (uint32_t)tc[5], (uint32_t)tc[6], (uint32_t)tc[7]);
                 st_async_b128(irow + 20, (uint32_t)tc[8], 0u, 0u, 0u);
-                st_async_u8(b_state + rec, 0u);
-                st_async_u32(b_target + rec, 0xFFFFFFFFu);
+                // the placement words: parent, divide number, length, state
+                // (BS_PENDING); no target, no claim key yet
+                static_assert(BI_PARENT == 24 && BI_SEQ == 25 && BI_LEN == 26 && BI_STATE == 27 &&
+                              BI_TARGET == 28 && BI_PRIO == 30, "b_inh row: placement quads");
+                st_async_b128(irow + BI_PARENT, (uint32_t)cell, (uint32_t)nd, (uint32_t)len, 0u);
+                st_async_b128(irow + BI_TARGET, 0xFFFFFFFFu, 0u, 0u, 0u);
               }
             }
 #pragma unroll

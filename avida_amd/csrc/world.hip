@@ -916,24 +916,52 @@ __device__ __forceinline__ unsigned long long tile_merged(const DevWorld& W, int
 // task counts (main/cPhenotype.cc:824-1000) are the extra blocks'
 // (finalize_phenotype), off the pick's dependency chain.  BI_FINAL stays set
 // (a row is rewritten whole by its next divide): both halves test it.
-__device__ __forceinline__ void finalize_key(const DevWorld& W, int64_t r, int parent) {
-  int32_t* row = W.b_inh + r * BI_WORDS;
-  if ((row[BI_FINAL] & 1) == 0) return;
-  uint32_t clo, chi;
-  derive_key(W.rng[parent], W.rng[W.n + parent], W.b_seq[r], 0x1B873593U, clo, chi);
-  row[BI_RLO] = (int32_t)clo;
-  row[BI_RHI] = (int32_t)chi;
+// The words of a record's row that placement works with, in registers: a
+// placement kernel loads them (three quads, all in flight together) before
+// it tests anything, and passes on what it changed instead of loading it back.
+struct PlaceRow {
+  uint32_t lo, hi, ctr, fin;        // BI_RLO, BI_RHI, BI_RCTR, BI_FINAL
+  int parent;
+  uint32_t seq;
+  int len, state, target;           // BI_PARENT .. BI_TARGET
+  unsigned long long prio;          // BI_PRIO
+};
+__device__ __forceinline__ PlaceRow place_row(const DevWorld& W, int64_t r) {
+  static_assert(BI_RLO == 8 && BI_RHI == 9 && BI_RCTR == 10 && BI_FINAL == 11 && BI_PARENT == 24 && BI_SEQ == 25 &&
+                BI_LEN == 26 && BI_STATE == 27 && BI_TARGET == 28 && BI_PRIO == 30, "row quads");
+  const int4* q = reinterpret_cast<const int4*>(W.b_inh + r * BI_WORDS);
+  const int4 q2 = q[2], q6 = q[6], q7 = q[7];
+  PlaceRow p;
+  p.lo = (uint32_t)q2.x; p.hi = (uint32_t)q2.y; p.ctr = (uint32_t)q2.z; p.fin = (uint32_t)q2.w;
+  p.parent = q6.x; p.seq = (uint32_t)q6.y; p.len = q6.z; p.state = q6.w;
+  p.target = q7.x;
+  p.prio = (unsigned long long)(uint32_t)q7.z | ((unsigned long long)(uint32_t)q7.w << 32);
+  return p;
 }
-// (every load it needs is issued before the first test: the record's row, its
-// parent and sequence number, then the parent's divide count -- a chain of
-// three dependent loads after the queue entry)
+__device__ __forceinline__ void set_state(const DevWorld& W, int64_t r, int st) {
+  W.b_inh[r * BI_WORDS + BI_STATE] = st;
+}
+// (rlo, rhi: the parent's RNG key words, loaded by the caller with the pick's
+// other second-hop loads; the derived key is stored for activation and left
+// in p for the pick's draws)
+__device__ __forceinline__ void finalize_key(const DevWorld& W, int64_t r, PlaceRow& p, uint32_t rlo, uint32_t rhi) {
+  if ((p.fin & 1u) == 0u) return;
+  int32_t* row = W.b_inh + r * BI_WORDS;
+  derive_key(rlo, rhi, p.seq, 0x1B873593U, p.lo, p.hi);
+  row[BI_RLO] = (int32_t)p.lo;
+  row[BI_RHI] = (int32_t)p.hi;
+}
+// (every load it needs is issued before the first test: the record's row with
+// its parent and sequence number, then the parent's divide count -- a chain
+// of two dependent loads after the queue entry)
 __device__ __forceinline__ void finalize_phenotype(const DevWorld& W, int64_t r) {
-  static_assert(BI_LTASK == 12 && BI_FINAL == 11 && AVGPU_NUM_LOGIC_TASKS <= 12, "row quads");
+  static_assert(BI_LTASK == 12 && BI_FINAL == 11 && AVGPU_NUM_LOGIC_TASKS <= 12 && BI_PARENT == 24 && BI_SEQ == 25,
+                "row quads");
   int32_t* row = W.b_inh + r * BI_WORDS;
   const int4* q = reinterpret_cast<const int4*>(row);
-  const int4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
-  const int parent = W.b_parent[r];
-  const int seq = (int)W.b_seq[r];
+  const int4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5], q6 = q[6];
+  const int parent = q6.x;
+  const int seq = q6.y;
   if ((q2.w & 1) == 0) return;                 // BI_FINAL
   const int nd = W.num_div[parent];
   const double merit = __hiloint2double(q0.y, q0.x);
@@ -970,7 +998,7 @@ __device__ __forceinline__ uint32_t key_time(unsigned long long k) {
   const uint32_t tk = (uint32_t)(k >> 48);
   return key_kill(k) ? tk : 0xFFFFu - tk;
 }
-// record states (b_state)
+// record states (the row's BI_STATE word)
 enum : int8_t { BS_PENDING = 0, BS_WON = 1 /* 1 + round */, BS_KILL_LOST = 8 /* 8 + round */,
                 BS_CANCELLED = -1, BS_NO_CELL = -2 /* - round: found no cell in that round */ };
 __device__ __forceinline__ uint32_t rec_time(const DevWorld& W, int64_t r) {
@@ -1022,21 +1050,73 @@ __device__ __forceinline__ double position_value(const DevWorld& W, int c) {
 // claimed by earlier births -- GetUInt(size); without PREFER_EMPTY
 // GetUInt(size), redrawn while it is the parent and ALLOW_PARENT is 0.
 // Single worlds only (capi refuses strip tiles).
+// What a pick reads beyond the record's row, all of it addressed by the
+// row's parent alone and so loaded in one batch (one round trip): the
+// parent's RNG key words (round 0: finalize_key), and the occupancy -- for
+// m > 0 also round m - 1's claims -- of the eight neighbour cells and of the
+// parent's own cell.  The candidate list and the chosen cell's taken bit then
+// come from registers.  (A tile's taken() is tile_taken, which reads the halo
+// for edge and ghost cells: it keeps its own loads, one cell after the other.)
+struct PickIn {
+  uint32_t rlo, rhi;     // the parent's RNG key words
+  int nbr[8];            // births.h neighbours_mask
+  uint32_t valid, tk;    // bit k: slot k exists / is taken (slot 8: the parent's cell)
+};
 template <bool TILE>
-__device__ __forceinline__ bool place_pick_one(const DevWorld& W, int64_t r, int m) {
-  const int parent = W.b_parent[r];
-  if (m == 0) finalize_key(W, r, parent);   // round 0: the record's first draws
-  const unsigned long long* prev = m > 0 ? W.claim_r[m - 1] : nullptr;
-  auto taken = [&](int c) -> bool {
-    if (TILE) return tile_taken(W, c, m);
-    return W.occ[c] != 0 || (prev && prev[c] != 0ull);
+__device__ __forceinline__ PickIn pick_loads(const DevWorld& W, int parent, int m) {
+  PickIn in;
+  in.rlo = in.rhi = 0u;
+  in.valid = in.tk = 0u;
+  if (m == 0) { in.rlo = W.rng[parent]; in.rhi = W.rng[W.n + parent]; }
+  if (!TILE && W.birth_method == 4) {          // the soup draws its cell: no neighbourhood
+#pragma unroll
+    for (int k = 0; k < 8; k++) in.nbr[k] = parent;
+    return in;
+  }
+  in.valid = neighbours_mask(W, parent, in.nbr);
+  if (TILE) {
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+      if ((in.valid >> k) & 1u) in.tk |= (tile_taken(W, in.nbr[k], m) ? 1u : 0u) << k;
+    in.tk |= (tile_taken(W, parent, m) ? 1u : 0u) << 8;
+    return in;
+  }
+  uint8_t o[9];
+  unsigned long long c[9];
+#pragma unroll
+  for (int k = 0; k < 8; k++) o[k] = W.occ[in.nbr[k]];
+  o[8] = W.occ[parent];
+#pragma unroll
+  for (int k = 0; k < 9; k++) c[k] = 0ull;
+  if (m > 0) {
+    const unsigned long long* prev = W.claim_r[m - 1];
+#pragma unroll
+    for (int k = 0; k < 8; k++) c[k] = prev[in.nbr[k]];
+    c[8] = prev[parent];
+  }
+#pragma unroll
+  for (int k = 0; k < 9; k++) in.tk |= ((o[k] != 0 || c[k] != 0ull) ? 1u : 0u) << k;
+  return in;
+}
+// p: the record's row, in: pick_loads of its parent.  A pick leaves its target
+// and claim key in p (and in the row, one 16-B store) for the caller's atomics.
+template <bool TILE>
+__device__ __forceinline__ bool place_pick_one(const DevWorld& W, int64_t r, int m, PlaceRow& p, const PickIn& in) {
+  int32_t* const row = W.b_inh + r * BI_WORDS;
+  const int parent = p.parent;
+  if (m == 0) finalize_key(W, r, p, in.rlo, in.rhi);   // round 0: the record's first draws
+  const uint32_t lo = p.lo, hi = p.hi;
+  uint32_t ctr = p.ctr;
+  auto no_cell = [&]() {
+    p.target = -1;
+    p.state = BS_NO_CELL - m;
+    row[BI_TARGET] = -1;
+    row[BI_STATE] = p.state;
   };
+  int t = parent;
+  bool tkn = false;
   if (!TILE && W.birth_method == 4) {
-    int32_t* const inh = W.b_inh + (int64_t)r * BI_WORDS;
-    const uint32_t lo = (uint32_t)inh[BI_RLO], hi = (uint32_t)inh[BI_RHI];
-    uint32_t ctr = (uint32_t)inh[BI_RCTR];
     const uint32_t n = (uint32_t)W.n;
-    int t = -1;
     if (W.prefer_empty) {
       const uint32_t ne = (uint32_t)W.e_blk[(W.n + 255) / 256];
       t = ne > 0u ? W.e_list[rng_below(lo, hi, ctr, ne)] : (int)rng_below(lo, hi, ctr, n);
@@ -1045,63 +1125,74 @@ __device__ __forceinline__ bool place_pick_one(const DevWorld& W, int64_t r, int
       while (!W.allow_parent && n > 1u && t == parent) t = (int)rng_below(lo, hi, ctr, n);
     }
     if (t == parent && !W.allow_parent) {              // ActivateOffspring drops it (:706-713)
-      inh[BI_RCTR] = (int32_t)ctr;
-      W.b_target[r] = -1;
-      W.b_state[r] = (int8_t)(BS_NO_CELL - m);
+      p.ctr = ctr;
+      row[BI_RCTR] = (int32_t)ctr;
+      no_cell();
       return false;
     }
-    const unsigned long long key = claim_key(BI_TIME(inh[BI_FINAL]), taken(t), rng_next(lo, hi, ctr),
-                                             W.cell0 + parent, W.b_seq[r]);
-    inh[BI_RCTR] = (int32_t)ctr;
-    W.b_target[r] = t;
-    W.b_prio[r] = key;
-    W.b_tgt[(int64_t)m * W.rcap + r] = t;
-    return true;
-  }
-  int nbr[8];
-  const int nn = neighbours(W, parent, nbr);
-  int cand[9];
-  int nc = 0;
-  if (W.prefer_empty)
-    for (int k = 0; k < nn; k++)
-      if (!taken(nbr[k])) cand[nc++] = nbr[k];
-  if (nc == 0 && (W.birth_method == 1 || W.birth_method == 2)) {
-    // PositionAge / PositionMerit (main/cPopulation.cc:5416-5470): the parent
-    // first, valued -1 without ALLOW_PARENT; a neighbour of a larger value
-    // replaces the list, one of an equal value joins it (oracle place_pick)
-    double best = W.allow_parent ? position_value(W, parent) : -1.0;
-    cand[nc++] = parent;
-    for (int k = 0; k < nn; k++) {
-      const double v = position_value(W, nbr[k]);
-      if (v > best) { best = v; nc = 0; cand[nc++] = nbr[k]; }
-      else if (v == best) cand[nc++] = nbr[k];
+    tkn = W.occ[t] != 0 || (m > 0 && W.claim_r[m - 1][t] != 0ull);
+  } else {
+    const uint32_t nbrs = in.valid & 0xFFu;
+    uint32_t cm = W.prefer_empty ? nbrs & ~in.tk : 0u;   // candidate slots, in list order
+    int sel = 8;
+    if (cm == 0u && (W.birth_method == 1 || W.birth_method == 2)) {
+      // PositionAge / PositionMerit (main/cPopulation.cc:5416-5470): the parent
+      // first, valued -1 without ALLOW_PARENT; a neighbour of a larger value
+      // replaces the list, one of an equal value joins it (oracle place_pick)
+      int cs[9];
+      int nc = 0;
+      double best = W.allow_parent ? position_value(W, parent) : -1.0;
+      cs[nc++] = 8;
+      for (int k = 0; k < 8; k++) {
+        if (!((nbrs >> k) & 1u)) continue;
+        const double v = position_value(W, in.nbr[k]);
+        if (v > best) { best = v; nc = 0; cs[nc++] = k; }
+        else if (v == best) cs[nc++] = k;
+      }
+      sel = cs[rng_below(lo, hi, ctr, (uint32_t)nc)];
+    } else {
+      if (cm == 0u && W.birth_method != 3) cm = nbrs | (W.allow_parent ? 0x100u : 0u);
+      if (cm == 0u) {                          // the parent's cell, without a draw
+        if (!W.allow_parent) { no_cell(); return false; }
+      } else {
+        const int j = (int)rng_below(lo, hi, ctr, (uint32_t)__popc(cm));
+        int cnt = 0;
+#pragma unroll
+        for (int k = 0; k < 9; k++)
+          if ((cm >> k) & 1u) { if (cnt == j) sel = k; cnt++; }
+      }
     }
-  } else if (nc == 0 && W.birth_method != 3) {
-    for (int k = 0; k < nn; k++) cand[nc++] = nbr[k];
-    if (W.allow_parent) cand[nc++] = parent;
+    tkn = ((in.tk >> 8) & 1u) != 0u;
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+      if (sel == k) { t = in.nbr[k]; tkn = ((in.tk >> k) & 1u) != 0u; }
   }
-  if (nc == 0 && !W.allow_parent) {
-    W.b_target[r] = -1;
-    W.b_state[r] = (int8_t)(BS_NO_CELL - m);
-    return false;
-  }
-  int32_t* const inh = W.b_inh + (int64_t)r * BI_WORDS;
-  const uint32_t lo = (uint32_t)inh[BI_RLO], hi = (uint32_t)inh[BI_RHI];
-  uint32_t ctr = (uint32_t)inh[BI_RCTR];
-  const int t = nc > 0 ? cand[rng_below(lo, hi, ctr, (uint32_t)nc)] : parent;
-  const unsigned long long key = claim_key(BI_TIME(inh[BI_FINAL]), taken(t), rng_next(lo, hi, ctr),
-                                           W.cell0 + parent, W.b_seq[r]);
-  inh[BI_RCTR] = (int32_t)ctr;
-  W.b_target[r] = t;
-  W.b_prio[r] = key;
+  const unsigned long long key = claim_key(BI_TIME(p.fin), tkn, rng_next(lo, hi, ctr), W.cell0 + parent, p.seq);
+  p.ctr = ctr;
+  p.target = t;
+  p.prio = key;
+  row[BI_RCTR] = (int32_t)ctr;
+  *reinterpret_cast<int4*>(row + BI_TARGET) = make_int4(t, 0, (int)(uint32_t)key, (int)(uint32_t)(key >> 32));
   W.b_tgt[(int64_t)m * W.rcap + r] = t;
   return true;
 }
 
 // grid-stride over the birth queue (its length is only known on the device)
-#define QUEUE_LOOP(i) \
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, _qn = queue_len(W); i < _qn; \
-       i += (int64_t)gridDim.x * blockDim.x)
+// with the lane's record id r of entry i.  The list entry is loaded ahead:
+// b_list[i]'s address needs neither of the queue's lengths, so it is issued
+// together with them instead of a round trip behind them (queue_len ->
+// rec_of); an entry past the primary records reads a clamped slot that is
+// not used.
+__device__ __forceinline__ int list_entry(const DevWorld& W, int64_t i) { return W.b_list[i < W.n ? i : W.n - 1]; }
+__device__ __forceinline__ int64_t rec_from(const DevWorld& W, int64_t i, int64_t p, int64_t e) {
+  return i < p ? e : W.n + (i - p);
+}
+#define QUEUE_RECS(i, r, first, stride) \
+  for (int64_t i = (first), _qs = (stride), _e = list_entry(W, i), _p = W.b_count[BQ_PRIMARY], \
+               _qn = queue_len(W), r = rec_from(W, i, _p, _e); \
+       i < _qn; i += _qs, _e = i < _qn ? list_entry(W, i) : 0, r = rec_from(W, i, _p, _e))
+#define QUEUE_LOOP(i, r) \
+  QUEUE_RECS(i, r, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x)
 // BIRTH_METHOD 4 + PREFER_EMPTY: round m's candidates, ascending -- the cells
 // empty at placement start (after the slices' deaths) and, for m > 0, not
 // claimed in round m - 1 (FindRandEmptyCell's; oracle place_reset /
@@ -1111,8 +1202,14 @@ __device__ __forceinline__ bool place_pick_one(const DevWorld& W, int64_t r, int
 __device__ __forceinline__ bool soup_free(const DevWorld& W, int64_t c, int m) {
   return c < W.n && W.occ[c] == 0 && (m == 0 || W.claim_r[m - 1][c] == 0ull);
 }
+// (round m >= 2 of a launch k_place_round skips -- nobody picked in round
+// m - 1 -- has no pick to serve: the three kernels return at once)
+__device__ __forceinline__ bool soup_round_skipped(const DevWorld& W, int m) {
+  return m > 1 && W.b_count[BQ_PICKED + m - 1] == 0;
+}
 __global__ __launch_bounds__(256) void k_empty_count(DevWorld W, int m) {
   __shared__ int ws[4];
+  if (soup_round_skipped(W, m)) return;
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool e = soup_free(W, c, m);
   const int cnt = __popcll(__ballot(e));
@@ -1120,8 +1217,9 @@ __global__ __launch_bounds__(256) void k_empty_count(DevWorld W, int m) {
   __syncthreads();
   if (threadIdx.x == 0) W.e_blk[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
 }
-__global__ __launch_bounds__(1024) void k_empty_scan(DevWorld W, int nb) {
+__global__ __launch_bounds__(1024) void k_empty_scan(DevWorld W, int nb, int m) {
   __shared__ int part[1024];
+  if (soup_round_skipped(W, m)) return;
   const int per = (nb + 1023) / 1024;
   const int b0 = (int)threadIdx.x * per, b1 = min(nb, b0 + per);
   int sum = 0;
@@ -1144,6 +1242,7 @@ __global__ __launch_bounds__(1024) void k_empty_scan(DevWorld W, int nb) {
 }
 __global__ __launch_bounds__(256) void k_empty_scatter(DevWorld W, int m) {
   __shared__ int ws[4];
+  if (soup_round_skipped(W, m)) return;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const bool e = soup_free(W, c, m);
@@ -1170,18 +1269,23 @@ __device__ __forceinline__ void mutation_block(const DevWorld& W, int64_t blk, i
                                                uint8_t (*child)[TAPE_SLOT + 16]) {
   __shared__ int ml[MUT_PER_BLOCK][8];   // record (2 words), e0..e4, len0 | len << 16
   __shared__ int mn;
-  const int nb = queue_len(W);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  // (the lane's list entry is loaded ahead, with the queue's lengths: list_entry)
+  int64_t le = lane < MUT_PER_WAVE ? list_entry(W, blk * MUT_PER_BLOCK + wv * MUT_PER_WAVE + lane) : 0;
+  const int64_t np = W.b_count[BQ_PRIMARY];
+  const int nb = queue_len(W);
   for (int64_t q0 = blk * MUT_PER_BLOCK; q0 < nb; q0 += nblk * MUT_PER_BLOCK) {   // block-uniform
     if (threadIdx.x == 0) mn = 0;
     __syncthreads();
     const int64_t q = q0 + wv * MUT_PER_WAVE + lane;
+    const int64_t r = rec_from(W, q, np, le);
+    const int64_t qx = q + nblk * MUT_PER_BLOCK;
+    le = (lane < MUT_PER_WAVE && qx < nb) ? list_entry(W, qx) : 0;
     if (lane < MUT_PER_WAVE && q < nb) {
-      const int64_t r = rec_of(W, q);
       int e[5];
 #pragma unroll
       for (int k = 0; k < 5; k++) e[k] = W.b_edit[(int64_t)k * W.rcap + r];
-      const int l0 = W.b_len0[r], l1 = W.b_len[r];
+      const int l0 = W.b_len0[r], l1 = W.b_inh[r * BI_WORDS + BI_LEN];
       int x = e[0] | e[1] | e[2] | e[3] | e[4];
       if (W.seg_any)
         for (int k = 0; k < NSEG; k++) x |= W.b_pcnt[(int64_t)k * W.rcap + r];
@@ -1211,22 +1315,53 @@ __device__ __forceinline__ void mutation_block(const DevWorld& W, int64_t blk, i
 // from an earlier round is later in time; a lost kill claim was placed and
 // overwritten by the later winner; a lost empty claim picks again, treating
 // every cell claimed in round m - 1 as taken (each has a winner).
+// A record is still BS_PENDING at launch m only if it picked in round m - 1:
+// each launch counts its pickers (b_count[BQ_PICKED + m], one atomic per
+// wave), and the next launch returns at once when that count is 0 -- in a
+// full world every claim is a kill claim, nothing picks again, and launches 2
+// and 3 have no record to look at.  (Round 0's pickers are the whole queue:
+// launch 1 always runs.)
+// Per record: the row (one hop), then round m - 1's claim on its target and
+// that cell's owner together, then the owner's time where there is one.
 __global__ void k_place_round(DevWorld W, int m) {
+  if (m > 1 && W.b_count[BQ_PICKED + m - 1] == 0) return;
   const unsigned long long* prev = W.claim_r[m - 1];
   unsigned long long* cur = W.claim_r[m];
-  QUEUE_LOOP(q) {
-    const int64_t r = rec_of(W, q);
-    if (W.b_state[r] != BS_PENDING) continue;
-    const int t = W.b_target[r];
-    const unsigned long long key = W.b_prio[r];
-    if (prev[t] == key) {                      // won round m-1
-      W.b_state[r] = (int8_t)(BS_WON + m - 1);
-      W.occ[t] = 1;
-      if (takes_cell(W, W.owner[t], rec_time(W, r))) W.owner[t] = (int)r;
-      continue;
-    }
-    if (key_kill(key)) { W.b_state[r] = (int8_t)(BS_KILL_LOST + m - 1); continue; }
-    if (place_pick_one<false>(W, r, m)) atomicMax(&cur[W.b_target[r]], W.b_prio[r]);
+  const int lane = threadIdx.x & 63;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t le = list_entry(W, (int64_t)blockIdx.x * blockDim.x + threadIdx.x);   // loaded ahead (list_entry)
+  const int64_t np = W.b_count[BQ_PRIMARY];
+  for (int64_t q0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x - lane, qn = queue_len(W); q0 < qn;
+       q0 += stride) {                            // wave-uniform: the ballot below takes every lane
+    const int64_t q = q0 + lane;
+    const int64_t r = rec_from(W, q, np, le);
+    le = q + stride < qn ? list_entry(W, q + stride) : 0;
+    bool picked = false;
+    do {
+      if (q >= qn) break;
+      PlaceRow p = place_row(W, r);
+      const bool pend = p.state == BS_PENDING;
+      // (a record that is not pending may have no target: its loads read cell 0)
+      const int t = pend && p.target >= 0 ? p.target : 0;
+      const unsigned long long pv = prev[t];
+      const int own = W.owner[t];
+      if (!pend) break;
+      const unsigned long long key = p.prio;
+      if (pv == key) {                           // won round m-1
+        set_state(W, r, BS_WON + m - 1);
+        W.occ[t] = 1;
+        if (takes_cell(W, own, BI_TIME(p.fin))) W.owner[t] = (int)r;
+        break;
+      }
+      if (key_kill(key)) { set_state(W, r, BS_KILL_LOST + m - 1); break; }
+      const PickIn in = pick_loads<false>(W, p.parent, m);
+      if (place_pick_one<false>(W, r, m, p, in)) {
+        atomicMax(&cur[p.target], p.prio);
+        picked = true;
+      }
+    } while (0);
+    const unsigned long long bm = __ballot(picked);
+    if (bm && lane == 0) atomicAdd(&W.b_count[BQ_PICKED + m], (int)__popcll(bm));
   }
 }
 // Launch 0b of a single world: a record whose parent's cell was killed before
@@ -1246,12 +1381,13 @@ __global__ void k_place_claim0(DevWorld W, long long* pred_out, long long pred_s
     __threadfence_system();
     __hip_atomic_store(pred_out + PRED_SEQ, pred_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
-  QUEUE_LOOP(q) {
-    const int64_t r = rec_of(W, q);
-    if (W.b_state[r] != BS_PENDING) continue;
-    const int p = W.b_parent[r];
-    if (W.killt[p] > 0x10000u - rec_time(W, r)) { W.b_state[r] = BS_CANCELLED; continue; }
-    atomicMax(&W.claim_r[0][W.b_target[r]], W.b_prio[r]);
+  // entry, row, the parent's kill time, the atomic: four hops
+  QUEUE_LOOP(q, r) {
+    const PlaceRow p = place_row(W, r);
+    const uint32_t kt = W.killt[p.parent];
+    if (p.state != BS_PENDING) continue;
+    if (kt > 0x10000u - BI_TIME(p.fin)) { set_state(W, r, BS_CANCELLED); continue; }
+    atomicMax(&W.claim_r[0][p.target], p.prio);
   }
 }
 // Launch 0 of a single world's placement with the divide mutations beside it:
@@ -1265,20 +1401,21 @@ __global__ void k_place_claim0(DevWorld W, long long* pred_out, long long pred_s
 // the AVGPU_SPLIT_PICK_MUT diagnostic build that times the three parts apart)
 __global__ __launch_bounds__(256) void k_place_pick_mut(DevWorld W, int pblocks, int fblocks, int boff, int nblocks) {
   __shared__ uint8_t child[4][TAPE_SLOT + 16];
-  const int nb = queue_len(W);
   const int bid = (int)blockIdx.x + boff;
   if (bid < pblocks) {
-    for (int64_t i = (int64_t)bid * 256 + threadIdx.x; i < nb; i += (int64_t)pblocks * 256) {
-      const int64_t r = rec_of(W, i);
-      if (!place_pick_one<false>(W, r, 0)) continue;
-      const unsigned long long key = W.b_prio[r];
-      if (key_kill(key)) atomicMax(&W.killt[W.b_target[r]], 0x10000u - key_time(key));
+    QUEUE_RECS(i, r, (int64_t)bid * 256 + threadIdx.x, (int64_t)pblocks * 256) {
+      // the queue entry, the row, the parent's RNG words with the nine cells'
+      // occupancy, then the stores and the atomic: four hops
+      PlaceRow p = place_row(W, r);
+      const PickIn in = pick_loads<false>(W, p.parent, 0);
+      if (!place_pick_one<false>(W, r, 0, p, in)) continue;
+      if (key_kill(p.prio)) atomicMax(&W.killt[p.target], 0x10000u - key_time(p.prio));
     }
     return;
   }
   if (bid < pblocks + fblocks) {               // deferred divides' phenotype half
-    for (int64_t i = (int64_t)(bid - pblocks) * 256 + threadIdx.x; i < nb; i += (int64_t)fblocks * 256)
-      finalize_phenotype(W, rec_of(W, i));
+    QUEUE_RECS(i, r, (int64_t)(bid - pblocks) * 256 + threadIdx.x, (int64_t)fblocks * 256)
+      finalize_phenotype(W, r);
     return;
   }
   pblocks += fblocks;
@@ -1296,9 +1433,8 @@ __global__ __launch_bounds__(256) void k_place_pick_mut(DevWorld W, int pblocks,
 __global__ __launch_bounds__(256) void k_tile_prep(DevWorld W, int mblocks, int fblocks) {
   __shared__ uint8_t child[4][TAPE_SLOT + 16];
   if ((int)blockIdx.x >= mblocks && (int)blockIdx.x < mblocks + fblocks) {
-    const int nb = queue_len(W);
-    for (int64_t i = (int64_t)(blockIdx.x - mblocks) * 256 + threadIdx.x; i < nb; i += (int64_t)fblocks * 256)
-      finalize_phenotype(W, rec_of(W, i));
+    QUEUE_RECS(i, r, (int64_t)(blockIdx.x - mblocks) * 256 + threadIdx.x, (int64_t)fblocks * 256)
+      finalize_phenotype(W, r);
     return;
   }
   if ((int)blockIdx.x < mblocks) {
@@ -1341,15 +1477,15 @@ __global__ __launch_bounds__(256) void k_tile_prep(DevWorld W, int mblocks, int 
 __global__ __launch_bounds__(256) void k_tile_round(DevWorld W, int m, int rblocks) {
   const int X = W.world_x;
   if ((int)blockIdx.x < rblocks) {
-    const int nb = queue_len(W);
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < nb; q += (int64_t)rblocks * blockDim.x) {
-      const int64_t r = rec_of(W, q);
-      if (W.b_state[r] != BS_PENDING) continue;
+    QUEUE_RECS(q, r, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)rblocks * blockDim.x) {
+      PlaceRow p = place_row(W, r);
+      if (p.state != BS_PENDING) continue;
       if (m == 0) {
-        if (!place_pick_one<true>(W, r, 0)) continue;
-        const unsigned long long key = W.b_prio[r];
+        const PickIn in = pick_loads<true>(W, p.parent, 0);
+        if (!place_pick_one<true>(W, r, 0, p, in)) continue;
+        const unsigned long long key = p.prio;
         if (!key_kill(key)) continue;
-        const int t = W.b_target[r];
+        const int t = p.target;
         const uint32_t kv = 0x10000u - key_time(key);
         if (t >= W.n) {
           const int64_t k = t - W.n;
@@ -1360,18 +1496,21 @@ __global__ __launch_bounds__(256) void k_tile_round(DevWorld W, int m, int rbloc
         }
         continue;
       }
-      const int t = W.b_target[r];
-      const unsigned long long key = W.b_prio[r];
+      const int t = p.target;
+      const unsigned long long key = p.prio;
+      const int own = W.owner[t];              // (with the merged claim's loads)
       if (tile_merged(W, t, m - 1) == key) {   // won round m - 1
-        W.b_state[r] = (int8_t)(BS_WON + m - 1);
+        set_state(W, r, BS_WON + m - 1);
         W.occ[t] = 1;
-        if (takes_cell(W, W.owner[t], rec_time(W, r))) W.owner[t] = (int)r;
+        if (takes_cell(W, own, BI_TIME(p.fin))) W.owner[t] = (int)r;
         continue;
       }
-      if (key_kill(key)) { W.b_state[r] = (int8_t)(BS_KILL_LOST + m - 1); continue; }
-      if (m < 4 && place_pick_one<true>(W, r, m)) {
-        const int nt = W.b_target[r];
-        const unsigned long long nk = W.b_prio[r];
+      if (key_kill(key)) { set_state(W, r, BS_KILL_LOST + m - 1); continue; }
+      if (m >= 4) continue;
+      const PickIn in = pick_loads<true>(W, p.parent, m);
+      if (place_pick_one<true>(W, r, m, p, in)) {
+        const int nt = p.target;
+        const unsigned long long nk = p.prio;
         atomicMax(&W.claim_r[m][nt], nk);
         int d, x;
         bool ghost;
@@ -1421,17 +1560,17 @@ __global__ __launch_bounds__(256) void k_tile_round(DevWorld W, int m, int rbloc
 __global__ __launch_bounds__(256) void k_tile_claim0(DevWorld W) {
   const int X = W.world_x;
   if (blockIdx.x == 0 && threadIdx.x < NUM_LISTS) W.class_count[threadIdx.x] = 0;
-  QUEUE_LOOP(q) {
-    const int64_t r = rec_of(W, q);
-    if (W.b_state[r] != BS_PENDING) continue;
-    const int p = W.b_parent[r];
+  QUEUE_LOOP(q, r) {
+    const PlaceRow pr = place_row(W, r);
+    const int p = pr.parent;
     uint32_t kt = W.killt[p];
+    if (pr.state != BS_PENDING) continue;
     int d, x;
     bool ghost;
     if (halo_slot(W, p, d, x, ghost)) kt = max(kt, halo_kt(W.h_recv[d], X)[x]);
-    if (kt > 0x10000u - rec_time(W, r)) { W.b_state[r] = BS_CANCELLED; continue; }
-    const int t = W.b_target[r];
-    const unsigned long long key = W.b_prio[r];
+    if (kt > 0x10000u - BI_TIME(pr.fin)) { set_state(W, r, BS_CANCELLED); continue; }
+    const int t = pr.target;
+    const unsigned long long key = pr.prio;
     atomicMax(&W.claim_r[0][t], key);
     if (halo_slot(W, t, d, x, ghost)) atomicMax(&halo_cl(W.h_send[d], X, 0, ghost ? 0 : 1)[x], key);
   }
@@ -1515,19 +1654,22 @@ __device__ __forceinline__ void newborn_enqueue(const DevWorld& W, int cell, int
 #define ACT_PRE 8    // 16-B quads of the offspring's genome k_activate loads ahead
 #endif
 __global__ __launch_bounds__(64) void k_activate(DevWorld W, int fused, uint32_t key, int sub, int nsub) {
+  const int lane = threadIdx.x & 63;
+  int64_t le = list_entry(W, (int64_t)blockIdx.x * 64 + lane);   // loaded ahead, with the lengths (list_entry)
+  const int64_t np = W.b_count[BQ_PRIMARY];
   const int nb = queue_len(W);
   const int64_t ncell = W.n + (W.tiled ? 2 * (int64_t)W.world_x : 0);
-  const int lane = threadIdx.x & 63;
   const double total = W.totals[TOT_DIV];
   const long long uds = sub_share((long long)W.totals[TOT_UD], sub, nsub);
   unsigned long long born = 0, over = 0, canc = 0, nocell = 0, bad = 0, wasted = 0, nbs = 0;
   long long carry = 0;
   for (int64_t q0 = (int64_t)blockIdx.x * 64; q0 < nb; q0 += (int64_t)gridDim.x * 64) {
     const int64_t q = q0 + lane;
+    const int64_t i = rec_from(W, q, np, le);
+    le = q + (int64_t)gridDim.x * 64 < nb ? list_entry(W, q + (int64_t)gridDim.x * 64) : 0;
     int nrow = -1, ncell_nb = 0;
     do {
       if (q >= nb) break;
-      const int64_t i = rec_of(W, q);
       // the genome's first 128 B, loaded before the claims decide whether the
       // record won (a dependent round trip less for the ~95 % that do; the
       // whole class-0 genome, 20 quads, measured no faster)
@@ -1535,11 +1677,25 @@ __global__ __launch_bounds__(64) void k_activate(DevWorld W, int fused, uint32_t
       uint4 pre[ACT_PRE];
 #pragma unroll
       for (int u = 0; u < ACT_PRE; u++) pre[u] = g4[u];
-      const int tgt = W.b_target[i];
-      const int8_t st = W.b_state[i];
-      Child b = child_of_record(W, i);
-      // the replaced organism's instructions, loaded with the claim words
-      const int ran = (tgt >= 0 && (int64_t)tgt < W.n) ? W.ran[tgt] : 0;
+      // the whole row with them: the phenotype, the parent's task counts and
+      // the placement words (target, state, claim key, length)
+      static_assert(BI_LTASK == 12 && AVGPU_NUM_LOGIC_TASKS <= 12 && BI_STATE == 27 && BI_TARGET == 28 && BI_PRIO == 30,
+                    "row quads");
+      const int4* rq = reinterpret_cast<const int4*>(W.b_inh + i * BI_WORDS);
+      const int4 q0 = rq[0], q1 = rq[1], q2 = rq[2], q3 = rq[3], q4 = rq[4], q5 = rq[5], q6 = rq[6], q7 = rq[7];
+      const int tgt = q7.x;
+      const int st = q6.w;
+      const unsigned long long prio = (unsigned long long)(uint32_t)q7.z | ((unsigned long long)(uint32_t)q7.w << 32);
+      Child b = child_of_row(W, i, q0, q1, q2, q6);
+      const int lt[12] = {q3.x, q3.y, q3.z, q3.w, q4.x, q4.y, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w};
+      // the second hop, everything the target addresses: the replaced
+      // organism's instructions, round 3's claim on the cell and its owner
+      // (a target out of range reads cell 0; it is never used)
+      const bool tin = tgt >= 0 && (int64_t)tgt < ncell;
+      const int64_t tl = tin ? tgt : 0;
+      const int ran = (tin && (int64_t)tgt < W.n) ? W.ran[tl] : 0;
+      const unsigned long long c3 = W.claim_r[3][tl];
+      const int own = W.owner[tl];
       const int lastr = last_claim_round(st);
       // the record's claims, round k's at b_tgt[k] (the last one its target);
       // a target out of range is a corrupt record: counted, never written
@@ -1555,19 +1711,18 @@ __global__ __launch_bounds__(64) void k_activate(DevWorld W, int fused, uint32_t
       const uint32_t t = 0x10000u - b.hs;
       bool won = false;
       if (fused == ACT_STRIP) {
-        won = st >= BS_WON && st < BS_WON + 4 && W.owner[tgt] == (int)i;
-      } else if (st == BS_PENDING) {
-        won = W.claim_r[3][tgt] == W.b_prio[i] && takes_cell(W, W.owner[tgt], t);
+        won = st >= BS_WON && st < BS_WON + 4 && own == (int)i;
+      } else if (st == BS_PENDING) {           // (the owner's time: the one further dependent load)
+        won = c3 == prio && takes_cell(W, own, t);
       } else if (st >= BS_WON && st < BS_WON + 4) {
-        const unsigned long long c3 = W.claim_r[3][tgt];
-        won = W.owner[tgt] == (int)i && !(c3 != 0ull && key_time(c3) >= t);
+        won = own == (int)i && !(c3 != 0ull && key_time(c3) >= t);
       }
       if (!won) { over++; break; }
       if (b.len < 0 || b.len > AVGPU_MAX_GENOME) { bad++; break; }   // (k_halo_pack skips it too)
       if (tgt >= W.n) break;                   // sent to the neighbouring tile
       born++;
       b.hs = 0;                                // it runs its share of this step instead (newborn pass)
-      setup_child_lane<ACT_PRE>(W, tgt, b, W.b_genome + i * TAPE_SLOT, pre);
+      setup_child_lane<ACT_PRE>(W, tgt, b, W.b_genome + i * TAPE_SLOT, pre, lt);
       nrow = newborn_setup(W, tgt, t, b.merit, b.len, key, uds, total, carry, wasted, ran);
       ncell_nb = tgt;
     } while (0);
@@ -1611,19 +1766,20 @@ __global__ __launch_bounds__(64) void k_halo_pack(DevWorld W) {
     int64_t mine = -1;
     if (q < nb) {
       const int64_t i = rec_of(W, q);
-      const int tgt = W.b_target[i];
-      const int8_t st = W.b_state[i];
+      const PlaceRow p = place_row(W, i);
+      const int tgt = p.target, st = p.state;
       // (a target past the ghost rows or a length out of range is a corrupt
       // record: counted in k_activate, which sees the same fields, never sent)
       if (st >= BS_WON && st < BS_WON + 4 && tgt >= W.n && (int64_t)tgt < W.n + 2 * (int64_t)X &&
-          W.b_len[i] >= 0 && W.b_len[i] <= AVGPU_MAX_GENOME && W.owner[tgt] == (int)i)
+          p.len >= 0 && p.len <= AVGPU_MAX_GENOME && W.owner[tgt] == (int)i)
         mine = i;
     }
     for (unsigned long long m = __ballot(mine >= 0); m; m &= m - 1ull) {
     const int64_t i = (int64_t)__shfl((long long)mine, __ffsll((long long)m) - 1);
-    const int tgt = W.b_target[i];
+    const PlaceRow pi = place_row(W, i);
+    const int tgt = pi.target;
     const int d = (tgt - (int)W.n) / X, col = (tgt - (int)W.n) - d * X;
-    const int len = W.b_len[i];
+    const int len = pi.len;
     HaloHdr* hdr = reinterpret_cast<HaloHdr*>(W.r_send[d]);
     HaloRec* recs = reinterpret_cast<HaloRec*>(W.r_send[d] + sizeof(HaloHdr));
     uint8_t* arena = W.r_send[d] + sizeof(HaloHdr) + (int64_t)X * sizeof(HaloRec);
@@ -1637,7 +1793,7 @@ __global__ __launch_bounds__(64) void k_halo_pack(DevWorld W) {
     const bool fits = (int64_t)off + len <= W.r_arena;
     if (lane == 0) {
       HaloRec r;
-      r.col = col; r.round = W.b_state[i] - BS_WON; r.len = fits ? len : -1;
+      r.col = col; r.round = pi.state - BS_WON; r.len = fits ? len : -1;
       const Child b = child_of_record(W, i);
       r.gen = b.gen; r.ccopied = b.ccopied; r.exec = b.exec; r.gest = b.gest;
       r.rng_lo = b.lo; r.rng_hi = b.hi; r.rng_ctr = b.ctr;
@@ -2034,7 +2190,7 @@ void launch_world_post(const DevWorld& W, hipStream_t s, uint32_t key, int sub, 
   auto soup_cells = [&](int m) {                    // the soup's candidates of round m (k_empty_*)
     const int eb = (int)nblk(W.n, 256);
     hipLaunchKernelGGL(k_empty_count, dim3(eb), dim3(256), 0, s, W, m);
-    hipLaunchKernelGGL(k_empty_scan, dim3(1), dim3(1024), 0, s, W, eb);
+    hipLaunchKernelGGL(k_empty_scan, dim3(1), dim3(1024), 0, s, W, eb, m);
     hipLaunchKernelGGL(k_empty_scatter, dim3(eb), dim3(256), 0, s, W, m);
   };
   if (soup) soup_cells(0);
