@@ -12,7 +12,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["interp.hip", "world.hip", "resources.hip", "genotypes.hip", "arbiter.hip", "landscape.hip", "capi.hip"]
+SOURCES = ["interp.hip", "world.hip", "resources.hip", "genotypes.hip", "arbiter.hip", "landscape.hip",
+           # the host side of the C ABI, one file per subsystem (csrc/host.h is what they share)
+           "capi.hip", "capi_serial.hip", "capi_systematics.hip", "capi_state.hip", "capi_landscape.hip",
+           "capi_resources.hip", "capi_tiles.hip"]
 OUT = os.path.join(HERE, "libavida_gpu.so")
 # diagnostic variant with per-phase s_memtime clocks (tools/phase_clocks.py only)
 OUT_CLK = os.path.join(HERE, "libavida_gpu_clk.so")
@@ -46,7 +49,7 @@ def build(force: bool = False, verbose: bool = False, clocks: bool = False) -> s
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
 
-    with ThreadPoolExecutor(len(SOURCES)) as ex:
+    with ThreadPoolExecutor(min(len(SOURCES), 16)) as ex:
         list(ex.map(compile_one, range(len(SOURCES))))
     cmd = [HIPCC, "--offload-arch=gfx950", "-fPIC", "-shared", "-o", out + ".tmp", *objs]
     if verbose:

@@ -280,6 +280,11 @@ def set_arbiter(lib, handle, rows, summary, sz_count):
                    "avgpu_set_arbiter")
 
 
+def live_objects(lib):
+    """Device buffers, pinned buffers, events and streams the library owns now (avgpu_live_objects)"""
+    return int(lib.avgpu_live_objects())
+
+
 # avgpu_landscape (include/avida_gpu.h): one row per base genome
 MAX_INST = 64
 LANDSCAPE_DTYPE = np.dtype([("total_count", "<i8"), ("dead_count", "<i8"), ("neg_count", "<i8"),
@@ -309,7 +314,7 @@ EXPORTED = [
     "avgpu_set_tile", "avgpu_tile_buffer_bytes", "avgpu_set_tile_buffers", "avgpu_tile_partials",
     "avgpu_tile_begin", "avgpu_tile_steps", "avgpu_tile_begin_step", "avgpu_tile_place", "avgpu_tile_finish", "avgpu_tile_res_bytes",
     "avgpu_set_tile_res_buffers", "avgpu_tile_res_cons", "avgpu_tile_res_settle",
-    "avgpu_last_step_insts", "avgpu_last_kernel_ms", "avgpu_kernel_times", "avgpu_counters",
+    "avgpu_last_step_insts", "avgpu_last_kernel_ms", "avgpu_kernel_times", "avgpu_counters", "avgpu_live_objects",
     "avgpu_state_digests", "avgpu_set_rng_mode", "avgpu_run_serial_updates", "avgpu_set_serial_streams",
     "avgpu_get_serial_state", "avgpu_set_serial_state", "avgpu_set_timing",
     "avgpu_get_genotypes", "avgpu_last_genotypes_ms",
@@ -560,6 +565,9 @@ def load_product(path=None):
     lib.avgpu_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
     lib.avgpu_set_timing.argtypes = [C.c_void_p, C.c_int]
     lib.avgpu_counters.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]
+    if p == LIB_PATH or hasattr(lib, "avgpu_live_objects"):   # (as the arbiter below: an earlier diagnostic build)
+        lib.avgpu_live_objects.restype = C.c_int64
+        lib.avgpu_live_objects.argtypes = []
     lib.avgpu_update_totals.argtypes = [C.c_void_p, C.c_void_p]
     lib.avgpu_update_run.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AvgpuUpdateStats)]
     lib.avgpu_set_stream.argtypes = [C.c_void_p, C.c_void_p]

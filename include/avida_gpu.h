@@ -997,6 +997,12 @@ enum avgpu_counter {
 };
 int avgpu_counters(avgpu_world* w, int cumulative, int64_t* out, int n);
 
+/* What the library owns in this process right now: device buffers, pinned
+ * buffers, events and streams, of every world together.  A world's creation
+ * and destruction, or a refused call, leave it where it was ("nothing leaks"
+ * as an exact count, independent of the card's free memory). */
+int64_t avgpu_live_objects(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,7 +69,7 @@ class Scenario:
             import bench
             self.env = files.parse_environment(bench.resource_env_text(side, side))
         elif env == "generic":
-            # IP_GENERIC: a twice-only requisite is outside the simple form (capi.hip:858-861, load_env:
+            # IP_GENERIC: a twice-only requisite is outside the simple form (capi.hip avgpu_load_env's `simple` loop:
             # of the requisites only max_count 1, the once mask, and INT32_MAX keep `simple`;
             # interp.hip:2614-2619 interp_of then chooses the generic kernel)
             for r in self.env:

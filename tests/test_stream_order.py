@@ -1,6 +1,6 @@
 """Stream ordering of the C-ABI's host calls: every copy an
 API call makes runs on the world's own (non-blocking) stream and is complete
-on return (capi.hip COPY_SYNC / SET_SYNC), so calls issued right behind
+on return (host.h COPY_SYNC / SET_SYNC), so calls issued right behind
 updates that are still queued -- avgpu_run_update(w, NULL) returns before its
 kernels finish -- see the world those updates leave, and the next update sees
 what the call wrote: avgpu_kill, avgpu_get_resources / avgpu_set_resources,
