@@ -239,6 +239,61 @@ def _arbiter_check(lib, rc, name):
     return rc
 
 
+# one genotype of the lineage store (the ancestry
+# Systematics::Genotype keeps, systematics/Genotype.cc:139-176): rows ascending
+# by id, parent_id 0 = injected, -1 = orphan; seq_off the birth genome's offset
+# in the store's arena (16-B aligned canonical codes), -1 = not captured;
+# update_deactivated -1 while the genotype is active
+LINEAGE_ROW_DTYPE = np.dtype([("genotype_key", "<u8"), ("id", "<i8"), ("parent_id", "<i8"), ("seq_off", "<i8"),
+                              ("update_born", "<i8"), ("update_deactivated", "<i8"), ("depth", "<i4"),
+                              ("genome_length", "<i4"), ("gen_born", "<i4"), ("reserved", "<i4")])
+assert LINEAGE_ROW_DTYPE.itemsize == 64
+LINEAGE_SUMMARY_DTYPE = np.dtype([("rows", "<i8"), ("active_rows", "<i8"), ("arena_bytes", "<i8"),
+                                  ("num_orphans", "<i8"), ("num_unsequenced", "<i8"), ("max_depth", "<i8"),
+                                  ("dropped_last_prune", "<i8"), ("reserved", "<i8")])
+assert LINEAGE_SUMMARY_DTYPE.itemsize == 64
+
+
+def _chk(lib, rc, what):
+    if rc < 0:
+        msg = lib.avgpu_last_error()
+        raise RuntimeError(f"{what} ({rc}): {msg.decode() if msg else ''}")
+    return rc
+
+
+def enable_lineage(lib, handle, on=True, rows_hint=0, arena_hint=0):
+    """avgpu_enable_lineage: the lineage store beside the device arbiter"""
+    _chk(lib, lib.avgpu_enable_lineage(handle, int(bool(on)), int(rows_hint), int(arena_hint)), "avgpu_enable_lineage")
+
+
+def get_lineage(lib, handle, summary_only=False):
+    """(rows, arena bytes, summary) of the store through avgpu_get_lineage"""
+    s = np.zeros(1, dtype=LINEAGE_SUMMARY_DTYPE)
+    _chk(lib, lib.avgpu_get_lineage(handle, None, 0, None, 0, s.ctypes.data_as(C.c_void_p)), "avgpu_get_lineage")
+    if summary_only:
+        return None, None, s[0]
+    rows = np.zeros(int(s[0]["rows"]), dtype=LINEAGE_ROW_DTYPE)
+    arena = np.zeros(max(1, int(s[0]["arena_bytes"])), dtype=np.uint8)
+    _chk(lib, lib.avgpu_get_lineage(handle, rows.ctypes.data_as(C.c_void_p), len(rows),
+                                     arena.ctypes.data_as(C.c_void_p), len(arena), None), "avgpu_get_lineage")
+    return rows, arena[:int(s[0]["arena_bytes"])], s[0]
+
+
+def set_lineage(lib, handle, rows, arena, summary):
+    rows = np.ascontiguousarray(rows, dtype=LINEAGE_ROW_DTYPE)
+    arena = np.ascontiguousarray(arena, dtype=np.uint8)
+    s = np.array([summary], dtype=LINEAGE_SUMMARY_DTYPE)
+    _chk(lib, lib.avgpu_set_lineage(handle, len(rows), rows.ctypes.data_as(C.c_void_p) if len(rows) else None,
+                                     arena.ctypes.data_as(C.c_void_p) if len(arena) else None, len(arena),
+                                     s.ctypes.data_as(C.c_void_p)), "avgpu_set_lineage")
+
+
+def prune_lineage(lib, handle):
+    s = np.zeros(1, dtype=LINEAGE_SUMMARY_DTYPE)
+    _chk(lib, lib.avgpu_prune_lineage(handle, s.ctypes.data_as(C.c_void_p)), "avgpu_prune_lineage")
+    return s[0]
+
+
 def classify_genotypes(lib, handle, update, threshold):
     """One classification on the device (avgpu_classify_genotypes): its
     summary, one ARBITER_SUMMARY_DTYPE record"""
@@ -320,6 +375,8 @@ EXPORTED = [
     "avgpu_get_genotypes", "avgpu_last_genotypes_ms",
     "avgpu_classify_genotypes", "avgpu_get_arbiter", "avgpu_set_arbiter", "avgpu_reset_arbiter",
     "avgpu_last_arbiter_ms",
+    "avgpu_get_parent_keys", "avgpu_set_parent_keys",
+    "avgpu_enable_lineage", "avgpu_get_lineage", "avgpu_set_lineage", "avgpu_prune_lineage", "avgpu_last_lineage_ms",
     "avgpu_landscapes", "avgpu_set_landscape_chunk", "avgpu_last_landscape_ms",
     "avgpu_landscapes_indel", "avgpu_landscape_pairs",
 ]
@@ -517,6 +574,8 @@ def bind_common(lib, prefix):
         "set_clock": (C.c_int, [V, C.POINTER(AvgpuUpdateStats)]),
         "get_census": (C.c_int, [V, I64, I64, V]),
         "set_genotype_keys": (C.c_int, [V, I64, I64, V]),
+        "get_parent_keys": (C.c_int, [V, I64, I64, V]),   # the product only (the oracle keeps no ancestry)
+        "set_parent_keys": (C.c_int, [V, I64, I64, V]),
         "state_digests": (C.c_int, [V, I64, I64, V]),
         "set_rng_mode": (C.c_int, [V, C.c_int, V, I64, V]),
         "set_serial_streams": (C.c_int, [V, V, I64, V, I64]),
@@ -588,6 +647,18 @@ def load_product(path=None):
         lib.avgpu_reset_arbiter.argtypes = [C.c_void_p]
         lib.avgpu_last_arbiter_ms.restype = C.c_int
         lib.avgpu_last_arbiter_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+    if p == LIB_PATH or hasattr(lib, "avgpu_enable_lineage"):   # the lineage store
+        V, I64 = C.c_void_p, C.c_int64
+        lib.avgpu_enable_lineage.restype = C.c_int
+        lib.avgpu_enable_lineage.argtypes = [V, C.c_int, I64, I64]
+        lib.avgpu_get_lineage.restype = C.c_int
+        lib.avgpu_get_lineage.argtypes = [V, V, I64, V, I64, V]
+        lib.avgpu_set_lineage.restype = C.c_int
+        lib.avgpu_set_lineage.argtypes = [V, I64, V, V, I64, V]
+        lib.avgpu_prune_lineage.restype = C.c_int
+        lib.avgpu_prune_lineage.argtypes = [V, V]
+        lib.avgpu_last_lineage_ms.restype = C.c_int
+        lib.avgpu_last_lineage_ms.argtypes = [V, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     # mutational landscapes: the product only (the oracle runs avida_amd.landscape.spec)
     lib.avgpu_landscapes.restype = C.c_int
     lib.avgpu_landscapes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int,

@@ -14,7 +14,12 @@ avgpu_cpu_state records), `tape` (one byte per site: op | copied << 6 |
 executed << 7, `cap` bytes per cell), `stats` (raw avgpu_update_stats),
 `levels` / `grids` (resources), `gkeys` (the census genotype keys of the
 birth genomes, which the tape no longer holds once an organism copied into
-its own sites; avgpu_set_genotype_keys), `serial` / `spec` / `face` /
+its own sites; avgpu_set_genotype_keys), `pkeys` (the product's parent keys,
+avgpu_get_parent_keys / avgpu_set_parent_keys: each organism's parent's
+genotype key; the oracle keeps none, and a file without them
+restores every organism as parentless), `lin_rows` / `lin_genomes` /
+`lin_summary` (the device lineage store where it is on, avgpu_get_lineage;
+restored through avgpu_set_lineage after the arbiter), `serial` / `spec` / `face` /
 `soup_perm` / `reaper` (the serial world's own state, avgpu_get_serial_state:
 its two streams' positions, speculative credits, connection-list rotations,
 BIRTH_METHOD 4's empty_cell_id_array and 5's reaper queue, rear first),
@@ -78,6 +83,10 @@ def save(lib, prefix, handle, ncells, nres, path):
           face.ctypes.data_as(C.c_void_p), soup.ctypes.data_as(C.c_void_p), reaper.ctypes.data_as(C.c_void_p),
           len(reaper))
     extra = {}
+    if prefix == "avgpu_" and hasattr(lib, "avgpu_get_parent_keys"):
+        pk = np.zeros(ncells, dtype=np.uint64)
+        _call(lib, prefix, "get_parent_keys", handle, 0, ncells, pk.ctypes.data_as(C.c_void_p))
+        extra["pkeys"] = pk
     if prefix == "avgpu_" and hasattr(lib, "avgpu_get_arbiter"):
         # the device-resident genotype arbiter's state (a strip tile keeps none)
         try:
@@ -86,7 +95,13 @@ def save(lib, prefix, handle, ncells, nres, path):
             if "strip tiles" not in str(e):
                 raise
         else:
-            extra = dict(arb_rows=rows.view(np.uint8), arb_summary=np.frombuffer(summary.tobytes(), dtype=np.uint8),
+            try:                                   # the lineage store, where it is on
+                lrows, larena, lsum = capi.get_lineage(lib, handle)
+                extra.update(lin_rows=lrows.view(np.uint8), lin_genomes=larena,
+                             lin_summary=np.frombuffer(lsum.tobytes(), dtype=np.uint8))
+            except (RuntimeError, AttributeError):
+                pass
+            extra = dict(extra, arb_rows=rows.view(np.uint8), arb_summary=np.frombuffer(summary.tobytes(), dtype=np.uint8),
                          arb_sz_count=sz)
     np.savez_compressed(path, **extra, states=np.frombuffer(st, dtype=np.uint8), tape=tape.astype(np.uint8), gkeys=gkeys,
                         serial=np.frombuffer(ser, dtype=np.uint8), spec=spec, face=face, soup_perm=soup,
@@ -130,6 +145,9 @@ def load(lib, prefix, handle, path):
     if "gkeys" in z.files:                     # genotype keys of the birth genomes
         gk = np.ascontiguousarray(z["gkeys"], dtype=np.uint64)
         _call(lib, prefix, "set_genotype_keys", handle, 0, ncells, gk.ctypes.data_as(C.c_void_p))
+    if "pkeys" in z.files and prefix == "avgpu_" and hasattr(lib, "avgpu_set_parent_keys"):
+        pk = np.ascontiguousarray(z["pkeys"], dtype=np.uint64)   # after set_states, which clears them
+        _call(lib, prefix, "set_parent_keys", handle, 0, ncells, pk.ctypes.data_as(C.c_void_p))
     if "serial" in z.files:                    # the serial world's own state (version >= 4)
         ser = _struct(capi.AvgpuSerialState, z["serial"].tobytes(), "serial state")
         arrs = [np.ascontiguousarray(z[k], dtype=t) for k, t in
@@ -139,6 +157,14 @@ def load(lib, prefix, handle, path):
         rows = np.frombuffer(z["arb_rows"].tobytes(), dtype=capi.ARBITER_ROW_DTYPE)
         summary = np.frombuffer(z["arb_summary"].tobytes(), dtype=capi.ARBITER_SUMMARY_DTYPE)[0]
         capi.set_arbiter(lib, handle, rows, summary, z["arb_sz_count"])
+        if "lin_rows" in z.files and hasattr(lib, "avgpu_set_lineage"):   # a world with the store on takes it
+            lrows = np.frombuffer(z["lin_rows"].tobytes(), dtype=capi.LINEAGE_ROW_DTYPE)
+            lsum = np.frombuffer(z["lin_summary"].tobytes(), dtype=capi.LINEAGE_SUMMARY_DTYPE)[0]
+            try:
+                capi.set_lineage(lib, handle, lrows, z["lin_genomes"], lsum)
+            except RuntimeError as e:
+                if "the store is off" not in str(e):
+                    raise
     stats = _struct(capi.AvgpuUpdateStats, z["stats"].tobytes(), "stats")
     _call(lib, prefix, "set_clock", handle, C.byref(stats))
     levels = np.ascontiguousarray(z["levels"], dtype=np.float64)

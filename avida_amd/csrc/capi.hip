@@ -22,7 +22,7 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   const avgpu_cfg& c = w->cfg;
   int rc = 0;
 #define A(ptr, cnt) if ((rc = w->alloc(&W.ptr, (size_t)(cnt))) < 0) return rc
-  A(xs, (size_t)n * XS_WORDS); A(ctl, n); A(mem_size, n); A(max_exec, n); A(age, n); A(birth_len, n); A(gkey, n); A(rng, 3 * n);
+  A(xs, (size_t)n * XS_WORDS); A(ctl, n); A(mem_size, n); A(max_exec, n); A(age, n); A(birth_len, n); A(gkey, n); A(pkey, n); A(rng, 3 * n);
   A(budget, n); A(aclass, n); A(tape, (size_t)n * TAPE_SLOT);
   A(inputs, 3 * n); A(last_task, AVGPU_MAX_REACTIONS * n);
   A(cur_react, AVGPU_MAX_REACTIONS * n);

@@ -168,6 +168,107 @@ static int arbiter_reserve(avgpu_world* w, int64_t rows, bool keep) {
   return 0;
 }
 
+// ---- the lineage store (lineage.hip) ----
+// room for `rows` rows (the stream is idle): 1.25x growth, the held rows kept
+static int lineage_reserve_rows(avgpu_world* w, int64_t rows) {
+  LinScratch& L = w->lin;
+  if (rows <= L.cap) return 0;
+  const int64_t want = std::max<int64_t>(rows + rows / 4, std::max<int64_t>(w->lin_rows_hint, 1));
+  DevBuf<avgpu_lineage_row> nb(w->stream);
+  int rc = nb.alloc((size_t)want);
+  if (rc < 0) return rc;
+  if (L.n > 0)
+    COPY_SYNC(w, nb.get(), L.rows, (size_t)L.n * sizeof(avgpu_lineage_row), hipMemcpyDeviceToDevice);
+  w->lin_rows = std::move(nb);
+  L.rows = w->lin_rows.get();
+  L.cap = want;
+  return 0;
+}
+static int lineage_reserve_arena(avgpu_world* w, int64_t bytes) {
+  LinScratch& L = w->lin;
+  if (bytes <= L.arena_cap) return 0;
+  const int64_t want = (std::max<int64_t>(bytes + bytes / 4, std::max<int64_t>(w->lin_arena_hint, 16)) + 15) & ~15ll;
+  DevBuf<uint8_t> nb(w->stream);
+  int rc = nb.alloc((size_t)want);
+  if (rc < 0) return rc;
+  if (L.arena_bytes > 0) COPY_SYNC(w, nb.get(), L.arena, (size_t)L.arena_bytes, hipMemcpyDeviceToDevice);
+  w->lin_arena = std::move(nb);
+  L.arena = w->lin_arena.get();
+  L.arena_cap = want;
+  return 0;
+}
+// the scratch rows of a classification (its new rows) or a prune (every row)
+static int lineage_reserve_scratch(avgpu_world* w, int64_t n) {
+  LinScratch& L = w->lin;
+  if (n <= L.scap) return 0;
+  const int64_t want = std::max<int64_t>(n + n / 4, 64);
+  HIPCHK(hipStreamSynchronize(w->stream));
+  int rc = w->lin_idx.alloc((size_t)want);
+  if (rc == 0) rc = w->lin_asz.alloc((size_t)want);
+  if (rc == 0) rc = w->lin_mark.alloc((size_t)want);
+  if (rc == 0) rc = w->lin_newcell.alloc((size_t)want);
+  L.idx = w->lin_idx.get(); L.asz = w->lin_asz.get(); L.mark = w->lin_mark.get(); L.newcell = w->lin_newcell.get();
+  L.scap = rc == 0 ? want : 0;
+  return rc;
+}
+static int lineage_clear(avgpu_world* w) {
+  LinScratch& L = w->lin;
+  L.n = 0;
+  L.arena_bytes = 0;
+  w->lin_dropped = 0;
+  if (L.ctr) SET_SYNC(w, L.ctr, 0, LIN_CTR_WORDS * sizeof(unsigned long long));
+  return 0;
+}
+static int lineage_summary(avgpu_world* w, avgpu_lineage_summary* s) {
+  LinScratch& L = w->lin;
+  unsigned long long c[LIN_CTR_WORDS];
+  HIPCHK(hipMemsetAsync(L.ctr + LIN_MAXDEPTH, 0, sizeof(unsigned long long), w->stream));
+  launch_lineage_max_depth(L, w->stream);
+  HIPCHK(hipGetLastError());
+  COPY_SYNC(w, c, L.ctr, sizeof(c), hipMemcpyDeviceToHost);
+  memset(s, 0, sizeof(*s));
+  s->rows = L.n;
+  s->active_rows = w->arb_ready ? w->arb_n : 0;
+  s->arena_bytes = L.arena_bytes;
+  s->num_orphans = (int64_t)c[LIN_ORPHANS];
+  s->num_unsequenced = (int64_t)c[LIN_UNSEQ];
+  s->max_depth = (int64_t)c[LIN_MAXDEPTH];
+  s->dropped_last_prune = w->lin_dropped;
+  return 0;
+}
+// one classification's store maintenance (the stream is idle; the arbiter's
+// buffers are swapped): n_prev rows and next id id0 before, m rows after
+static int lineage_step(avgpu_world* w, int64_t n_prev, int64_t id0, int64_t m, int64_t update) {
+  LinScratch& L = w->lin;
+  const int64_t n_new = w->arb_last.next_id - id0;
+  if (n_new < 0 || n_new > m) return fail(AVGPU_ESTATE, "lineage: new ids outside the classification");
+  int rc = lineage_reserve_rows(w, L.n + n_new);
+  if (rc == 0) rc = lineage_reserve_scratch(w, n_new);
+  if (rc < 0) return rc;
+  HIPCHK(hipEventRecord(w->ev_lin[0], w->stream));
+  launch_lineage_classify(L, w->arb, w->W, n_prev, m, id0, n_new, update, w->stream);
+  HIPCHK(hipGetLastError());
+  if (n_new > 0) {
+    unsigned long long total = 0;
+    COPY_SYNC(w, &total, L.ctr + LIN_TOTAL_A, sizeof(total), hipMemcpyDeviceToHost);
+    if ((int64_t)total < L.arena_bytes) return fail(AVGPU_ESTATE, "lineage: arena total went down");
+    if ((rc = lineage_reserve_arena(w, (int64_t)total)) < 0) return rc;
+    launch_lineage_copy(L, w->W, n_new, w->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(w->ev_lin[1], w->stream));
+    HIPCHK(hipStreamSynchronize(w->stream));
+    L.n += n_new;
+    L.arena_bytes = (int64_t)total;
+  } else {
+    HIPCHK(hipEventRecord(w->ev_lin[1], w->stream));
+    HIPCHK(hipStreamSynchronize(w->stream));
+  }
+  float ms = 0.f;
+  HIPCHK(hipEventElapsedTime(&ms, w->ev_lin[0], w->ev_lin[1]));
+  w->lin_ms = ms;
+  return 0;
+}
+
 int avgpu_classify_genotypes(avgpu_world* w, int64_t update, int32_t threshold, avgpu_arbiter_summary* out) {
   if (!w || !out || threshold < 1)
     return fail(AVGPU_EINVAL, "avgpu_classify_genotypes: NULL world, NULL out or threshold < 1");
@@ -178,6 +279,7 @@ int avgpu_classify_genotypes(avgpu_world* w, int64_t update, int32_t threshold, 
   if (rc < 0) return rc;
   const GtScratch& S = w->gt;
   ArbScratch& A = w->arb;
+  const int64_t lin_prev = w->arb_n, lin_id0 = w->arb_last.next_id;
   // the first part: the grouping; its totals are the summary's first fields
   HIPCHK(hipMemsetAsync(S.totals, 0, sizeof(avgpu_genotype_totals), w->stream));
   HIPCHK(hipEventRecord(w->ev_arb[0], w->stream));
@@ -213,6 +315,7 @@ int avgpu_classify_genotypes(avgpu_world* w, int64_t update, int32_t threshold, 
   HIPCHK(hipEventElapsedTime(&ms1, w->ev_arb[2], w->ev_arb[3]));
   w->arb_ms = (double)ms0 + (double)ms1;
   w->arb_bytes = sizeof(avgpu_arbiter_summary);
+  if (w->lin_on) return lineage_step(w, lin_prev, lin_id0, m, update);
   return 0;
 }
 
@@ -295,6 +398,7 @@ int avgpu_set_arbiter(avgpu_world* w, int64_t n, const avgpu_arbiter_row* rows,
   else
     HIPCHK(hipMemsetAsync(A.sz_count, 0, (AVGPU_MAX_GENOME + 1) * sizeof(int64_t), w->stream));
   HIPCHK(hipStreamSynchronize(w->stream));
+  if (w->lin_on && (rc = lineage_clear(w)) < 0) return rc;   // (a resume fills it again: avgpu_set_lineage)
   w->arb_n = n;
   w->arb_last = *summary;
   w->arb_last.num_genotypes = n;
@@ -325,6 +429,181 @@ int avgpu_set_genotype_keys(avgpu_world* w, int64_t first, int64_t count, const 
   if (count == 0) return 0;
   HIPCHK(hipMemcpyAsync(w->W.gkey + first, keys, count * sizeof(uint64_t), hipMemcpyHostToDevice, w->stream));
   HIPCHK(hipStreamSynchronize(w->stream));
+  return 0;
+}
+
+int avgpu_enable_lineage(avgpu_world* w, int on, int64_t rows_hint, int64_t arena_hint) {
+  if (!w || rows_hint < 0 || arena_hint < 0) return fail(AVGPU_EINVAL, "avgpu_enable_lineage: NULL world or a negative hint");
+  if (w->W.tiled) return fail(AVGPU_EUNSUPPORTED, "lineage store on strip tiles");
+  HIPCHK(hipStreamSynchronize(w->stream));
+  if (!on) {
+    w->lin_on = false;
+    w->lin_rows.reset(); w->lin_arena.reset(); w->lin_ctr.reset(); w->lin_idx.reset(); w->lin_asz.reset();
+    w->lin_mark.reset(); w->lin_newcell.reset();
+    w->lin = LinScratch{};
+    return 0;
+  }
+  if (w->arb_ready && (w->arb_n != 0 || w->arb_last.next_id != 1))
+    return fail(AVGPU_ESTATE, "avgpu_enable_lineage: the arbiter holds genotypes (avgpu_reset_arbiter first)");
+  if (w->lin_on) return 0;
+  int rc = w->lin_ctr.alloc(LIN_CTR_WORDS);
+  if (rc < 0) return rc;
+  w->lin = LinScratch{};
+  w->lin.ctr = w->lin_ctr.get();
+  w->lin_rows_hint = rows_hint > 0 ? rows_hint : 1024;
+  w->lin_arena_hint = arena_hint > 0 ? arena_hint : 65536;
+  for (Event& e : w->ev_lin)
+    if ((rc = e.create()) < 0) return rc;
+  w->lin_on = true;
+  w->lin_ms = w->lin_prune_ms = 0.0;
+  return lineage_clear(w);
+}
+
+int avgpu_get_lineage(avgpu_world* w, avgpu_lineage_row* rows, int64_t cap, uint8_t* genomes, int64_t genome_cap,
+                      avgpu_lineage_summary* summary) {
+  if (!w || cap < 0 || genome_cap < 0) return fail(AVGPU_EINVAL, "avgpu_get_lineage: NULL world or a negative cap");
+  if (w->W.tiled) return fail(AVGPU_EUNSUPPORTED, "lineage store on strip tiles");
+  if (!w->lin_on) return fail(AVGPU_ESTATE, "avgpu_get_lineage: the store is off (avgpu_enable_lineage)");
+  const LinScratch& L = w->lin;
+  if ((rows && cap < L.n) || (genomes && genome_cap < L.arena_bytes))
+    return fail(AVGPU_EINVAL, "avgpu_get_lineage: the store has " + std::to_string(L.n) + " rows and " +
+                                  std::to_string(L.arena_bytes) + " arena bytes");
+  if (summary) {
+    const int rc = lineage_summary(w, summary);
+    if (rc < 0) return rc;
+  }
+  if (rows && L.n > 0)
+    HIPCHK(hipMemcpyAsync(rows, L.rows, (size_t)L.n * sizeof(avgpu_lineage_row), hipMemcpyDeviceToHost, w->stream));
+  if (genomes && L.arena_bytes > 0)
+    HIPCHK(hipMemcpyAsync(genomes, L.arena, (size_t)L.arena_bytes, hipMemcpyDeviceToHost, w->stream));
+  HIPCHK(hipStreamSynchronize(w->stream));
+  return (int)L.n;
+}
+
+int avgpu_set_lineage(avgpu_world* w, int64_t n, const avgpu_lineage_row* rows, const uint8_t* genomes, int64_t bytes,
+                      const avgpu_lineage_summary* summary) {
+  if (!w || n < 0 || bytes < 0 || (n > 0 && !rows) || (bytes > 0 && !genomes) || !summary || (bytes & 15))
+    return fail(AVGPU_EINVAL, "avgpu_set_lineage: NULL world, rows, genomes or summary, a negative count, or bytes "
+                              "not a multiple of 16");
+  if (w->W.tiled) return fail(AVGPU_EUNSUPPORTED, "lineage store on strip tiles");
+  if (!w->lin_on) return fail(AVGPU_ESTATE, "avgpu_set_lineage: the store is off (avgpu_enable_lineage)");
+  if (summary->num_orphans < 0 || summary->num_unsequenced < 0)
+    return fail(AVGPU_EINVAL, "avgpu_set_lineage: negative counters");
+  auto find = [&](int64_t id) -> int64_t {
+    int64_t lo = 0, hi = n;
+    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (rows[mid].id < id) lo = mid + 1; else hi = mid; }
+    return (lo < n && rows[lo].id == id) ? lo : -1;
+  };
+  const int64_t next_id = w->arb_ready ? w->arb_last.next_id : 1;
+  int64_t at = 0, active = 0;
+  for (int64_t j = 0; j < n; j++) {
+    const avgpu_lineage_row& r = rows[j];
+    if (r.id < 1 || r.id >= next_id || (j > 0 && r.id <= rows[j - 1].id))
+      return fail(AVGPU_EINVAL, "avgpu_set_lineage: row " + std::to_string(j) + ": ids must ascend strictly inside 1..next_id-1");
+    if (r.parent_id >= r.id || r.parent_id < -1 || (r.parent_id > 0 && find(r.parent_id) < 0))
+      return fail(AVGPU_EINVAL, "avgpu_set_lineage: row " + std::to_string(j) + ": parent_id must be below id and present, 0 or -1");
+    if (r.genome_length < 0 || r.genome_length > AVGPU_MAX_GENOME || r.depth < 0)
+      return fail(AVGPU_EINVAL, "avgpu_set_lineage: row " + std::to_string(j) + ": genome_length or depth out of range");
+    if (r.seq_off != -1) {                         // in id order, 16-B aligned, back to back
+      if (r.seq_off != at) return fail(AVGPU_EINVAL, "avgpu_set_lineage: row " + std::to_string(j) + ": seq_off out of order");
+      at += ((int64_t)r.genome_length + 15) & ~15ll;
+      if (at > bytes) return fail(AVGPU_EINVAL, "avgpu_set_lineage: row " + std::to_string(j) + ": genome past the arena");
+    }
+    active += r.update_deactivated < 0;
+  }
+  if (at != bytes) return fail(AVGPU_EINVAL, "avgpu_set_lineage: the genomes do not fill the arena");
+  // every active arbiter id present as an active row, and no other active row
+  const int64_t m = w->arb_ready ? w->arb_n : 0;
+  std::vector<avgpu_arbiter_row> arows((size_t)m);
+  if (m > 0) COPY_SYNC(w, arows.data(), w->arb.row[w->arb.cur], (size_t)m * sizeof(avgpu_arbiter_row), hipMemcpyDeviceToHost);
+  for (int64_t j = 0; j < m; j++) {
+    const int64_t q = find(arows[(size_t)j].id);
+    if (q < 0 || rows[q].update_deactivated >= 0 || rows[q].genotype_key != arows[(size_t)j].genotype_key)
+      return fail(AVGPU_EINVAL, "avgpu_set_lineage: active genotype " + std::to_string(arows[(size_t)j].id) + " has no active row");
+  }
+  if (active != m) return fail(AVGPU_EINVAL, "avgpu_set_lineage: an active row without an active genotype");
+  HIPCHK(hipStreamSynchronize(w->stream));
+  LinScratch& L = w->lin;
+  const int64_t keep_n = L.n, keep_b = L.arena_bytes;
+  L.n = 0; L.arena_bytes = 0;                      // (nothing to carry over when a buffer grows)
+  int rc = lineage_reserve_rows(w, std::max<int64_t>(n, 1));
+  if (rc == 0) rc = lineage_reserve_arena(w, std::max<int64_t>(bytes, 16));
+  if (rc < 0) { L.n = keep_n; L.arena_bytes = keep_b; return rc; }
+  if (n > 0) HIPCHK(hipMemcpyAsync(L.rows, rows, (size_t)n * sizeof(avgpu_lineage_row), hipMemcpyHostToDevice, w->stream));
+  if (bytes > 0) HIPCHK(hipMemcpyAsync(L.arena, genomes, (size_t)bytes, hipMemcpyHostToDevice, w->stream));
+  unsigned long long c[LIN_CTR_WORDS] = {};
+  c[LIN_ORPHANS] = (unsigned long long)summary->num_orphans;
+  c[LIN_UNSEQ] = (unsigned long long)summary->num_unsequenced;
+  COPY_SYNC(w, L.ctr, c, sizeof(c), hipMemcpyHostToDevice);
+  L.n = n;
+  L.arena_bytes = bytes;
+  w->lin_dropped = summary->dropped_last_prune;
+  return 0;
+}
+
+int avgpu_prune_lineage(avgpu_world* w, avgpu_lineage_summary* summary) {
+  if (!w) return fail(AVGPU_EINVAL, "NULL world");
+  if (w->W.tiled) return fail(AVGPU_EUNSUPPORTED, "lineage store on strip tiles");
+  if (!w->lin_on) return fail(AVGPU_ESTATE, "avgpu_prune_lineage: the store is off (avgpu_enable_lineage)");
+  LinScratch& L = w->lin;
+  w->lin_dropped = 0;
+  w->lin_prune_ms = 0.0;
+  if (L.n > 0) {
+    int rc = lineage_reserve_scratch(w, L.n);
+    if (rc < 0) return rc;
+    HIPCHK(hipEventRecord(w->ev_lin[2], w->stream));
+    launch_lineage_mark(L, w->stream);
+    HIPCHK(hipGetLastError());
+    unsigned long long c[LIN_CTR_WORDS];
+    COPY_SYNC(w, c, L.ctr, sizeof(c), hipMemcpyDeviceToHost);
+    const int64_t kept = (int64_t)c[LIN_TOTAL_A], kbytes = (int64_t)c[LIN_TOTAL_B];
+    if (kept < 0 || kept > L.n || kbytes < 0 || kbytes > L.arena_bytes)
+      return fail(AVGPU_ESTATE, "lineage prune: totals outside the store");
+    // compacted into new buffers of the store's capacities, then swapped in
+    DevBuf<avgpu_lineage_row> nr(w->stream);
+    DevBuf<uint8_t> na(w->stream);
+    if ((rc = nr.alloc((size_t)L.cap)) < 0 || (rc = na.alloc((size_t)L.arena_cap)) < 0) return rc;
+    launch_lineage_compact(L, nr.get(), L.cap, na.get(), L.arena_cap, w->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(w->ev_lin[3], w->stream));
+    HIPCHK(hipStreamSynchronize(w->stream));
+    w->lin_rows = std::move(nr);
+    w->lin_arena = std::move(na);
+    L.rows = w->lin_rows.get();
+    L.arena = w->lin_arena.get();
+    w->lin_dropped = L.n - kept;
+    L.n = kept;
+    L.arena_bytes = kbytes;
+    float ms = 0.f;
+    HIPCHK(hipEventElapsedTime(&ms, w->ev_lin[2], w->ev_lin[3]));
+    w->lin_prune_ms = ms;
+  }
+  return summary ? lineage_summary(w, summary) : 0;
+}
+
+int avgpu_last_lineage_ms(avgpu_world* w, double* classify_ms, double* prune_ms) {
+  if (!w) return fail(AVGPU_EINVAL, "NULL world");
+  if (classify_ms) *classify_ms = w->lin_ms;
+  if (prune_ms) *prune_ms = w->lin_prune_ms;
+  return 0;
+}
+
+int avgpu_get_parent_keys(avgpu_world* w, int64_t first, int64_t count, uint64_t* out) {
+  if (!w || !out || first < 0 || count < 0 || first + count > w->W.n) return fail(AVGPU_EINVAL, "cell range");
+  if (count == 0) return 0;
+  DevBuf<uint64_t> d(w->stream);                  // (a dead cell's row is stale: masked on the device)
+  const int rc = d.alloc((size_t)count);
+  if (rc < 0) return rc;
+  launch_get_parent_keys(w->W, w->stream, first, count, d.get());
+  HIPCHK(hipGetLastError());
+  COPY_SYNC(w, out, d.get(), (size_t)count * sizeof(uint64_t), hipMemcpyDeviceToHost);
+  return 0;
+}
+
+int avgpu_set_parent_keys(avgpu_world* w, int64_t first, int64_t count, const uint64_t* keys) {
+  if (!w || !keys || first < 0 || count < 0 || first + count > w->W.n) return fail(AVGPU_EINVAL, "cell range");
+  if (count == 0) return 0;
+  COPY_SYNC(w, w->W.pkey + first, keys, (size_t)count * sizeof(uint64_t), hipMemcpyHostToDevice);
   return 0;
 }
 

@@ -30,6 +30,13 @@
 enum { BI_MERIT = 0, BI_FITNESS = 2, BI_GEN = 4, BI_CCOPIED = 5, BI_EXEC = 6, BI_GEST = 7,
        BI_RLO = 8, BI_RHI = 9, BI_RCTR = 10, BI_FINAL = 11, BI_LTASK = 12,
        BI_PARENT = 24, BI_SEQ = 25, BI_LEN = 26, BI_STATE = 27, BI_TARGET = 28, BI_PRIO = 30, BI_WORDS = 32 };
+// words 22..23, after the nine task counts (the divide stores them as 0): the
+// genotype key of the parent's birth genome (DevWorld::pkey), written by the
+// record's round-0 pick -- before any activation of the step can overwrite the
+// parent cell's gkey -- and read by activation with the task counts' quad
+enum { BI_PKEY = 22 };
+static_assert(BI_LTASK + AVGPU_NUM_LOGIC_TASKS <= BI_PKEY && BI_PKEY % 2 == 0 && BI_PKEY + 2 <= BI_PARENT,
+              "b_inh row: the parent's genotype key sits in the task quads' spare words, 8-B aligned");
 static_assert(BI_LTASK + 12 <= BI_PARENT && BI_PARENT % 4 == 0 && BI_TARGET % 4 == 0 && BI_PRIO % 2 == 0 &&
               BI_PRIO + 2 == BI_WORDS, "b_inh row: the placement words are its last two quads");
 #define BI_TIME(w) ((uint32_t)(w) >> 16)
@@ -344,9 +351,14 @@ struct DevWorld {
   // (PACC_* below, pacc_sum)
   long long* pacc;
   const double* totals;   // the step's totals (k_block_counts; TOT_* below)
+  // [n] the gkey of the parent's cell at the moment of the divide that put the
+  // organism here (the key of the parent's birth genome); 0
+  // for an injected / restored organism.  Placement and activation write it,
+  // the interpreter never touches it.
+  uint64_t* pkey;
 };
 // (the interpreter loads the fields by scalar offset: none may move)
-static_assert(sizeof(DevWorld) == 1616, "DevWorld's size");
+static_assert(sizeof(DevWorld) == 1624 && offsetof(DevWorld, pkey) == 1616, "DevWorld's size; pkey is appended");
 
 // ---------------------------------------------------------------------------
 // The scratch vectors the update's kernels and the host hand each other.  Each
@@ -508,6 +520,9 @@ struct HaloRec {
   double merit, fitness;
   int32_t last_task[AVGPU_NUM_LOGIC_TASKS], pad2[3];   // the parent's (SetupOffspring)
 };
+// pad2[0..1]: the parent's genotype key, low word first (4-B aligned: two words)
+static_assert(sizeof(HaloRec) == 112 && offsetof(HaloRec, last_task) == 64 && offsetof(HaloRec, pad2) == 100 &&
+              offsetof(HaloRec, merit) == 48 && offsetof(HaloRec, off) == 40, "HaloRec's layout is fixed");
 __host__ __device__ inline int64_t record_bytes(int x, int64_t arena) {
   return (int64_t)sizeof(HaloHdr) + (int64_t)x * (int64_t)sizeof(HaloRec) + arena;
 }
@@ -847,6 +862,7 @@ __device__ __forceinline__ void inject_org(const DevWorld& W, int64_t c, int len
   W.birth_len[c] = len;
   if (W.track_age) W.age[c] = -1;          // injected between updates: age 0 during the next one
   W.gkey[c] = gk_tape(t, len);
+  W.pkey[c] = 0ull;                         // no parent: injected
   // stream key (DESIGN.md RNG spec)
   uint32_t lo, hi, ctr = 0;
   derive_key(W.seed_lo, W.seed_hi, (uint32_t)(W.cell0 + c), 0xA5A5A5A5U, lo, hi);
@@ -982,6 +998,7 @@ void launch_set_states(const DevWorld& W, hipStream_t s, int64_t first, int64_t 
                        const uint8_t* codes, int cap);
 void launch_state_digest(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, uint64_t* d_out);
 void launch_get_census(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, avgpu_census* d_out);
+void launch_get_parent_keys(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, uint64_t* d_out);
 // the genotype table (genotypes.hip).  GtAgg: what a run of
 // sorted positions of one genome key adds up to; GtScratch: the world's
 // scratch for the grouping, allocated at the first avgpu_get_genotypes.
@@ -1050,6 +1067,34 @@ void launch_arbiter_begin(const ArbScratch& A, const GtScratch& S, int64_t updat
 // every id of the new state is below 2^id_bits (<= 50).
 void launch_arbiter_classify(const ArbScratch& A, const GtScratch& S, const avgpu_genotype* d_tab, int64_t m,
                              int64_t n_prev, int64_t update, int32_t threshold, int id_bits, hipStream_t s);
+// the lineage store beside the arbiter (lineage.hip): the view
+// a launch takes by value, assigned where a buffer is (re)allocated
+static_assert(sizeof(avgpu_lineage_row) == 64 && sizeof(avgpu_lineage_summary) == 64, "lineage rows");
+enum { LIN_ORPHANS = 0, LIN_UNSEQ = 1, LIN_TOTAL_A = 2, LIN_TOTAL_B = 3, LIN_MAXDEPTH = 4, LIN_CTR_WORDS = 8 };
+struct LinScratch {
+  avgpu_lineage_row* rows;  // [cap] ascending by id
+  int64_t n, cap;
+  uint8_t* arena;           // [arena_cap] captured birth genomes, 16-B aligned offsets in id order
+  int64_t arena_bytes, arena_cap;
+  unsigned long long* ctr;  // [LIN_CTR_WORDS] (LIN_* above; the first two cumulative)
+  int64_t* idx;             // [scap] scratch: sizes / positions (scans)
+  int64_t* asz;             // [scap] scratch: arena sizes of a prune
+  uint32_t* mark;           // [scap] a prune's mark words
+  int32_t* newcell;         // [scap] first cell of each new row of a classification
+  int64_t scap;
+};
+// one classification's store maintenance, after launch_arbiter_classify and
+// the swap of A.cur: n_prev rows before, m after, ids id0 .. id0 + n_new - 1
+// new; leaves the arena total in ctr[LIN_TOTAL_A] for the host to reserve,
+// then launch_lineage_copy captures the genomes
+void launch_lineage_classify(const LinScratch& L, const ArbScratch& A, const DevWorld& W, int64_t n_prev, int64_t m,
+                             int64_t id0, int64_t n_new, int64_t update, hipStream_t s);
+void launch_lineage_copy(const LinScratch& L, const DevWorld& W, int64_t n_new, hipStream_t s);
+// a prune: marks, positions (ctr[LIN_TOTAL_A] rows kept, ctr[LIN_TOTAL_B] arena bytes kept), then the compaction
+void launch_lineage_mark(const LinScratch& L, hipStream_t s);
+void launch_lineage_compact(const LinScratch& L, avgpu_lineage_row* out, int64_t out_cap, uint8_t* out_arena,
+                            int64_t out_arena_cap, hipStream_t s);
+void launch_lineage_max_depth(const LinScratch& L, hipStream_t s);
 // mutational landscapes (landscape.hip).  The mutants of every
 // base genome are numbered back to back: mutant m of the call is rank
 // m - mut_off[g] of genome g.  Ranks are cut into tiles of LAND_TILE aligned

@@ -253,6 +253,19 @@ struct avgpu_world {
   avh::Event ev_arb[4];
   double arb_ms = 0.0;
   int64_t arb_bytes = 0;
+  // the lineage store (avgpu_enable_lineage; lineage.hip): lin is the view the
+  // launches take, assigned where a buffer is (re)allocated
+  bool lin_on = false;
+  LinScratch lin = {};
+  avh::DevBuf<avgpu_lineage_row> lin_rows;
+  avh::DevBuf<uint8_t> lin_arena;
+  avh::DevBuf<unsigned long long> lin_ctr;
+  avh::DevBuf<int64_t> lin_idx, lin_asz;
+  avh::DevBuf<uint32_t> lin_mark;
+  avh::DevBuf<int32_t> lin_newcell;
+  int64_t lin_rows_hint = 0, lin_arena_hint = 0, lin_dropped = 0;
+  avh::Event ev_lin[4];
+  double lin_ms = 0.0, lin_prune_ms = 0.0;
   // mutational landscapes (avgpu_landscapes): the scratch test world of
   // land_chunk cells the mutants run through and the per-chunk scratch (in its
   // allocs), created by the first call, re-created when land_chunk changes

@@ -2527,9 +2527,11 @@ __global__ __launch_bounds__(64, 1) void k_serial_update(const DevWorld* __restr
         Child b = child_of_record(W, c);
         b.inputs = in3;                                          // from the context stream (lane 0's)
         b.hs = 0;                                                // placed at once: no head start
+        const uint64_t pk = W.gkey[c];                           // the parent's genotype key (t may be c)
         setup_child<64>(W, t, b, reinterpret_cast<const uint32_t*>(W.b_genome + c * TAPE_SLOT), lane);
         __threadfence_block();
         if (lane == 0) {
+          W.pkey[t] = pk;
           W.spec[t] = 0;                                         // InsertOrganism resets the credit
           if (parent_alive && face_t >= 0) W.face[t] = (uint8_t)face_t;
           if (W.birth_method == 5) {                             // ActivateOrganism: Push(target) (:1358-1361)

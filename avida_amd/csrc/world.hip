@@ -273,6 +273,7 @@ __global__ void k_set_states(DevWorld W, int64_t first, int64_t count, const avg
     gs += gk_word(v, w, s.birth_length);
   }
   W.gkey[c] = gk_final(gs, s.birth_length);
+  W.pkey[c] = 0ull;   // (a checkpoint sets the parent keys after the states: avgpu_set_parent_keys)
 }
 
 // systematics census (include/avida_gpu.h avgpu_census): one row per cell,
@@ -296,6 +297,14 @@ __global__ void k_census(DevWorld W, int64_t first, int64_t count, avgpu_census*
     r.num_divides = (ctl & CTL_FRESH) ? 0 : W.num_div[c];
   }
   out[i] = r;
+}
+
+// the parent keys of a cell range, a dead cell's (stale) word masked to 0
+__global__ void k_parent_keys(DevWorld W, int64_t first, int64_t count, uint64_t* out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const int64_t c = first + i;
+  out[i] = (W.ctl[c] & CTL_ALIVE) ? W.pkey[c] : 0ull;
 }
 
 // budget = uniform or per-cell array, all live cells of [first, first+count)
@@ -959,6 +968,9 @@ __device__ __forceinline__ void finalize_phenotype(const DevWorld& W, int64_t r)
                 "row quads");
   int32_t* row = W.b_inh + r * BI_WORDS;
   const int4* q = reinterpret_cast<const int4*>(row);
+  // (q5's last two words, BI_PKEY, are being written by this launch's pick
+  // blocks: loaded with the quad, never used -- lt[] is read up to
+  // AVGPU_NUM_LOGIC_TASKS = 9 only)
   const int4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5], q6 = q[6];
   const int parent = q6.x;
   const int seq = q6.y;
@@ -1059,6 +1071,7 @@ __device__ __forceinline__ double position_value(const DevWorld& W, int c) {
 // for edge and ghost cells: it keeps its own loads, one cell after the other.)
 struct PickIn {
   uint32_t rlo, rhi;     // the parent's RNG key words
+  uint64_t pk;           // round 0: the parent cell's genotype key (the record's BI_PKEY words)
   int nbr[8];            // births.h neighbours_mask
   uint32_t valid, tk;    // bit k: slot k exists / is taken (slot 8: the parent's cell)
 };
@@ -1067,7 +1080,8 @@ __device__ __forceinline__ PickIn pick_loads(const DevWorld& W, int parent, int 
   PickIn in;
   in.rlo = in.rhi = 0u;
   in.valid = in.tk = 0u;
-  if (m == 0) { in.rlo = W.rng[parent]; in.rhi = W.rng[W.n + parent]; }
+  in.pk = 0ull;
+  if (m == 0) { in.rlo = W.rng[parent]; in.rhi = W.rng[W.n + parent]; in.pk = W.gkey[parent]; }
   if (!TILE && W.birth_method == 4) {          // the soup draws its cell: no neighbourhood
 #pragma unroll
     for (int k = 0; k < 8; k++) in.nbr[k] = parent;
@@ -1104,7 +1118,12 @@ template <bool TILE>
 __device__ __forceinline__ bool place_pick_one(const DevWorld& W, int64_t r, int m, PlaceRow& p, const PickIn& in) {
   int32_t* const row = W.b_inh + r * BI_WORDS;
   const int parent = p.parent;
-  if (m == 0) finalize_key(W, r, p, in.rlo, in.rhi);   // round 0: the record's first draws
+  if (m == 0) {
+    finalize_key(W, r, p, in.rlo, in.rhi);             // round 0: the record's first draws
+    // the parent's genotype key, while its cell still holds it (no activation
+    // of this step has run: a later one may overwrite that cell)
+    *reinterpret_cast<uint64_t*>(row + BI_PKEY) = in.pk;
+  }
   const uint32_t lo = p.lo, hi = p.hi;
   uint32_t ctr = p.ctr;
   auto no_cell = [&]() {
@@ -1723,6 +1742,8 @@ __global__ __launch_bounds__(64) void k_activate(DevWorld W, int fused, uint32_t
       born++;
       b.hs = 0;                                // it runs its share of this step instead (newborn pass)
       setup_child_lane<ACT_PRE>(W, tgt, b, W.b_genome + i * TAPE_SLOT, pre, lt);
+      static_assert(BI_PKEY == 22, "the parent's key: the last two words of q5");
+      W.pkey[tgt] = (uint64_t)(uint32_t)q5.z | ((uint64_t)(uint32_t)q5.w << 32);
       nrow = newborn_setup(W, tgt, t, b.merit, b.len, key, uds, total, carry, wasted, ran);
       ncell_nb = tgt;
     } while (0);
@@ -1800,7 +1821,9 @@ __global__ __launch_bounds__(64) void k_halo_pack(DevWorld W) {
       r.off = off; r.t = 0x10000u - b.hs; r.merit = b.merit; r.fitness = b.fitness;
 #pragma unroll
       for (int t = 0; t < AVGPU_NUM_LOGIC_TASKS; t++) r.last_task[t] = b.ltask[t];
-      r.pad2[0] = r.pad2[1] = r.pad2[2] = 0;
+      r.pad2[0] = W.b_inh[i * BI_WORDS + BI_PKEY];       // the parent's genotype key
+      r.pad2[1] = W.b_inh[i * BI_WORDS + BI_PKEY + 1];
+      r.pad2[2] = 0;
       recs[slot] = r;
       if (!fits) atomicAdd(&hdr->overflow, 1);
     }
@@ -1859,6 +1882,7 @@ __global__ __launch_bounds__(64) void k_activate_remote(DevWorld W, uint32_t key
     const int ran = W.ran[c];
     setup_child<64>(W, c, b, reinterpret_cast<const uint32_t*>(arena + r.off), lane);
     if (lane == 0) {
+      W.pkey[c] = (uint64_t)(uint32_t)r.pad2[0] | ((uint64_t)(uint32_t)r.pad2[1] << 32);
       const int row = newborn_setup(W, c, r.t, r.merit, r.len, key, uds, total, carry, wasted, ran);
       if (row >= 0) {
         nbs++;
@@ -2039,6 +2063,10 @@ void launch_state_digest(const DevWorld& W, hipStream_t s, int64_t first, int64_
 void launch_get_census(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, avgpu_census* d_out) {
   if (count <= 0) return;
   k_census<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(W, first, count, d_out);
+}
+void launch_get_parent_keys(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, uint64_t* d_out) {
+  if (count <= 0) return;
+  k_parent_keys<<<(unsigned)((count + 255) / 256), 256, 0, s>>>(W, first, count, d_out);
 }
 void launch_set_states(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, const avgpu_cpu_state* in,
                        const uint8_t* codes, int cap) {

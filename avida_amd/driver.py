@@ -99,6 +99,14 @@ class ProductWorld:
     def census(self, first=0, count=None):
         return capi.get_census(self.lib, self.p, self.h, first, self.ncells - first if count is None else count)
 
+    def parent_keys(self, first=0, count=None):
+        """each cell's organism's parent's genotype key, 0 for an injected
+        organism or a dead cell (avgpu_get_parent_keys)"""
+        import numpy as np
+        out = np.zeros(self.ncells - first if count is None else count, dtype=np.uint64)
+        self._call("get_parent_keys", self.h, first, len(out), out.ctypes.data_as(C.c_void_p))
+        return out
+
     def genotypes(self):
         """(table, totals): the census grouped by key on the device
         (avgpu_get_genotypes)"""
@@ -108,6 +116,16 @@ class ProductWorld:
         """one classification by the arbiter kept on the device
         (avgpu_classify_genotypes): its summary record"""
         return capi.classify_genotypes(self.lib, self.h, update, threshold)
+
+    def enable_lineage(self, on=True, rows_hint=0, arena_hint=0):
+        capi.enable_lineage(self.lib, self.h, on, rows_hint, arena_hint)
+
+    def lineage_state(self, summary_only=False):
+        """(rows, arena, summary) of the device lineage store (avgpu_get_lineage)"""
+        return capi.get_lineage(self.lib, self.h, summary_only)
+
+    def prune_lineage(self):
+        return capi.prune_lineage(self.lib, self.h)
 
     def arbiter_state(self):
         """(rows, table, summary, sz_count) of the last classification
@@ -168,7 +186,7 @@ def _fires(trigger, start, u):
 
 
 class Driver:
-    def __init__(self, config_dir, data_dir, make_world=None, seed=None):
+    def __init__(self, config_dir, data_dir, make_world=None, seed=None, lineage=False):
         self.config_dir = config_dir
         acfg, self.iset, self.env, self.events = load_config(config_dir)
         self.cfg = capi.cfg_from_avida(acfg, seed=seed)
@@ -182,6 +200,15 @@ class Driver:
         kind = systematics.DeviceGenotypeArbiter if hasattr(self.world, "classify_genotypes") \
             else systematics.GenotypeArbiter
         self.arbiter = kind(int(acfg.get("THRESHOLD", 3))) if any(e[2] in need for e in self.events) else None
+        # lineage=True: ancestry (parents, depth, lineages) in the store
+        # the device keeps beside its arbiter
+        self.lineage = bool(lineage)
+        if self.lineage:
+            if not hasattr(self.world, "parent_keys") or not hasattr(self.world, "enable_lineage"):
+                raise ValueError(f"lineage=True needs a world that records parent keys; "
+                                 f"{type(self.world).__name__} has none")
+            self.arbiter = systematics.DeviceGenotypeArbiter(int(acfg.get("THRESHOLD", 3)), lineage=True)
+            self.arbiter.enable(self.world)
         self.rec.arbiter = self.arbiter
         self.done = False
         self.update = -1
@@ -238,9 +265,13 @@ class Driver:
             self.rec.print_resource(w.resources()[0], *args[:1])
         elif action == "SavePopulation":          # actions/SaveLoadActions.cc:168-176
             name = args[0] if args else "detail"
+            historic = int(args[1]) != 0 if len(args) > 1 else True      # save_historic (SaveLoadActions.cc:142)
+            if self.lineage and historic:
+                self.arbiter.prune()                # the historic rows written: the living genotypes' ancestors
             population.save_population(w, self.iset, self.arbiter,
                                        os.path.join(self.data_dir, f"{name}-{max(self.update, 0)}.spop"),
-                                       max(self.update, 0))
+                                       max(self.update, 0),
+                                       lineage=self.arbiter.lineage_store() if self.lineage and historic else None)
         elif action == "LoadPopulation":          # actions/SaveLoadActions.cc:62-88
             if len(args) > 1 and int(args[1]) >= 0:
                 self.update = int(args[1]) - 1     # SetCurrentUpdate: the next update is that one

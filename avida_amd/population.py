@@ -19,8 +19,14 @@ total_units length merit gest_time fitness gen_born update_born
 update_deactivated depth hw_type inst_set sequence) plus cells, gest_offset
 (each organism's CPU cycles into its gestation, :6330) and lineage.  Genotype
 ids and averages come from the host genotype classification
-(avida_amd/systematics.py); the hot path keeps no lineage, so parents are
-"(none)", gen_born / depth 0 and src "div:int".  The sequence is a member's
+(avida_amd/systematics.py).  Without a lineage store parents are "(none)",
+gen_born / depth 0 and src "div:int"; with one (save_population(...,
+lineage=store), a systematics.LineageStore: DESIGN.md 10.6) the rows carry
+parents, gen_born, update_deactivated and depth, and after the living
+genotypes come the store's historic rows -- the dead ancestors it kept -- with
+num_units 0 and no cells, as SavePopulation does with save_historic
+(main/cPopulation.cc:6490).  A historic genotype whose birth genome was not
+captured is written with the sequence "-".  The sequence is a member's
 birth genome: the device keeps only its key, so the first member whose tape
 prefix still hashes to the genotype's key provides it (an organism that copied
 into its own first sites cannot).
@@ -92,9 +98,10 @@ def load_population(world, iset: files.InstSet, path, ncells, cellid_offset=0):
     return len(cells)
 
 
-def save_population(world, iset: files.InstSet, arbiter, path, update, cap=capi.MAX_GENOME):
+def save_population(world, iset: files.InstSet, arbiter, path, update, cap=capi.MAX_GENOME, lineage=None):
     """cPopulation::SavePopulation (structured save) of `world` after
-    `update`; `arbiter` = the driver's GenotypeArbiter, updated this update."""
+    `update`; `arbiter` = the driver's GenotypeArbiter, updated this update;
+    `lineage` = its LineageStore for the ancestry columns and historic rows."""
     census = world.census()
     if arbiter is None:
         arbiter = systematics.GenotypeArbiter()
@@ -121,10 +128,26 @@ def save_population(world, iset: files.InstSet, arbiter, path, update, cap=capi.
             c = cells[0]
             seq = iset.to_sequence(ops[c * cap:c * cap + st[c].birth_length])
         merit, gest, fit, _, _, _ = arbiter.genotype_averages(g)
-        rows.append([g.id, "div:int", "(none)", "(none)", g.num_units, max(g.total_units, g.num_units),
-                     g.length, "%g" % merit, "%g" % gest, "%g" % fit, 0, g.update_born, -1, 0, 0, inst_set,
+        parents, gen_born, depth = "(none)", 0, 0
+        if lineage is not None:
+            lr = lineage.rows[lineage.index(g.id)]
+            parents = str(int(lr["parent_id"])) if lr["parent_id"] > 0 else "(none)"
+            gen_born, depth = int(lr["gen_born"]), int(lr["depth"])
+        rows.append([g.id, "div:int", "(none)", parents, g.num_units, max(g.total_units, g.num_units),
+                     g.length, "%g" % merit, "%g" % gest, "%g" % fit, gen_born, g.update_born, -1, depth, 0, inst_set,
                      seq, ",".join(map(str, cells)), ",".join(map(str, offsets)),
                      ",".join("0" for _ in cells)])
+    if lineage is not None:                   # the historic genotypes: dead, kept for a living descendant
+        op_of = {}
+        for op, hcode in enumerate(handlers):
+            op_of.setdefault(hcode, op)
+        for lr in lineage.rows[lineage.rows["update_deactivated"] >= 0]:
+            codes = lineage.sequence(int(lr["id"]))
+            seq = iset.to_sequence(bytes(op_of[c] for c in codes)) if codes is not None else "-"
+            rows.append([int(lr["id"]), "div:int", "(none)",
+                         str(int(lr["parent_id"])) if lr["parent_id"] > 0 else "(none)", 0, 0,
+                         int(lr["genome_length"]), 0, 0, 0, int(lr["gen_born"]), int(lr["update_born"]),
+                         int(lr["update_deactivated"]), int(lr["depth"]), 0, inst_set, seq])
     cols = ["ID", "Source", "Source Args", "Parent ID(s)", "Number of currently living organisms",
             "Total number of organisms that ever existed", "Genome Length", "Average Merit",
             "Average Gestation Time", "Average Fitness", "Generation Born", "Update Born",

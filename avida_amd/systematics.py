@@ -23,10 +23,15 @@ and only a summary returns per classification.  Rules:
 
 * a key not among the active genotypes becomes a new genotype; new ids are
   handed out in order of the first cell holding the key;
-* a genotype whose abundance falls to 0 is removed (no lineage / passive
-  references are kept -- the hot path records no parent genotype); a later
-  organism with the same genome starts a new genotype, as in the reference
-  once the old one left the active hash;
+* a genotype whose abundance falls to 0 is removed from the active set; a
+  later organism with the same genome starts a new genotype, as in the
+  reference once the old one left the active hash;
+* ancestry (GenotypeArbiter(threshold, lineage=True)): the
+  device hands every organism its parent's genotype key (avgpu_get_parent_keys),
+  and LineageStore keeps one row per genotype ever classified -- parent id,
+  depth = the parent's + 1 (systematics/Genotype.cc:139-176), the update it
+  was deactivated -- until prune() drops the dead genotypes with no living
+  descendant (the passive references of :159 and GenotypeArbiter.cc:499-530);
 * threshold: abundance >= THRESHOLD, or the genotype is the most abundant
   (GenotypeArbiter.cc:320-328, :459-467); names are given in id order among
   the genotypes that cross it in one update;
@@ -161,6 +166,120 @@ def cells_by_key(census):
     return ks[heads], alive[o], np.r_[heads, len(ks)]
 
 
+def _align16(n):
+    return (n + 15) & ~15
+
+
+class LineageStore:
+    """The ancestry of every genotype classified since the arbiter was new
+    (DESIGN.md 10.6): `rows` (capi.LINEAGE_ROW_DTYPE, ascending by id -- ids
+    are handed out consecutively, so appending keeps them sorted and a lookup
+    is a binary search) and `arena`, the captured birth genomes as canonical
+    codes at 16-B aligned offsets in id order.  Integers only; every rule is
+    order-free."""
+
+    def __init__(self):
+        self.rows = np.zeros(0, dtype=capi.LINEAGE_ROW_DTYPE)
+        self.arena = bytearray()
+        self.num_orphans = 0
+        self.num_unsequenced = 0
+        self.dropped_last_prune = 0
+
+    def index(self, gid):
+        """the row of genotype id `gid`, -1 when the store has none"""
+        ids = self.rows["id"]
+        j = int(np.searchsorted(ids, gid))
+        return j if j < len(ids) and int(ids[j]) == int(gid) else -1
+
+    def summary(self):
+        r = self.rows
+        return dict(rows=len(r), active_rows=int((r["update_deactivated"] < 0).sum()), arena_bytes=len(self.arena),
+                    num_orphans=self.num_orphans, num_unsequenced=self.num_unsequenced,
+                    max_depth=int(r["depth"].max()) if len(r) else 0, dropped_last_prune=self.dropped_last_prune)
+
+    def deactivate(self, ids, update):
+        """rule 1: the genotypes `ids` left the active set at `update`"""
+        if len(ids):
+            j = np.searchsorted(self.rows["id"], ids)
+            self.rows["update_deactivated"][j] = update
+
+    def append(self, new, old_keys, old_ids, update):
+        """rules 2 and 3: `new` = (key, id, parent key, genome length,
+        generation, sequence or None) per new genotype, ascending by id;
+        old_keys (ascending) / old_ids: the genotypes active BEFORE this
+        classification, those it deactivates included"""
+        add = np.zeros(len(new), dtype=capi.LINEAGE_ROW_DTYPE)
+        for k, (key, gid, pk, length, gen, seq) in enumerate(new):
+            parent_id, depth = 0, 0
+            if pk != 0:
+                j = int(np.searchsorted(old_keys, np.uint64(pk)))
+                if j < len(old_keys) and int(old_keys[j]) == int(pk):
+                    parent_id = int(old_ids[j])
+                    depth = int(self.rows["depth"][self.index(parent_id)]) + 1
+                else:            # born and gone between two classifications, or the key itself
+                    parent_id = -1
+                    self.num_orphans += 1
+            off = -1
+            if seq is not None and len(seq) == length and genome_key(seq) == int(key):
+                off = len(self.arena)
+                self.arena += bytes(c & 0x3F for c in seq) + bytes(_align16(length) - length)
+            else:
+                self.num_unsequenced += 1
+            add[k] = (key, gid, parent_id, off, update, -1, depth, length, gen, 0)
+        self.rows = np.concatenate([self.rows, add])
+
+    def kept_by_prune(self):
+        """the rows a prune keeps: the active ones and every row on the
+        parent_id chain of one (a closure: independent of the order walked)"""
+        r = self.rows
+        keep = r["update_deactivated"] < 0
+        for j in np.flatnonzero(keep):
+            p = int(r["parent_id"][j])
+            while p > 0:
+                q = self.index(p)
+                if q < 0 or keep[q]:
+                    break            # absent (pruned before), or already marked: its chain is, or will be
+                keep[q] = True
+                p = int(r["parent_id"][q])
+        return keep
+
+    def prune(self):
+        """rule 4: drop the dead genotypes without a living descendant; rows
+        and arena compacted stably (same order, offsets recomputed)"""
+        keep = self.kept_by_prune()
+        rows = self.rows[keep].copy()
+        arena = bytearray()
+        for j in range(len(rows)):
+            off = int(rows["seq_off"][j])
+            if off >= 0:
+                n = _align16(int(rows["genome_length"][j]))
+                rows["seq_off"][j] = len(arena)
+                arena += self.arena[off:off + n]
+        self.dropped_last_prune = int(len(self.rows) - len(rows))
+        self.rows, self.arena = rows, arena
+        return self.dropped_last_prune
+
+    def sequence(self, gid):
+        """the captured birth genome of genotype `gid` (canonical codes), or None"""
+        j = self.index(gid)
+        if j < 0 or self.rows["seq_off"][j] < 0:
+            return None
+        off = int(self.rows["seq_off"][j])
+        return bytes(self.arena[off:off + int(self.rows["genome_length"][j])])
+
+    def lineage_of(self, gid):
+        """the rows from genotype `gid` up to its root: each one's parent
+        follows it, until a row without a stored parent (parent_id 0: an
+        injected genotype; -1: an orphan; or a parent pruned away)"""
+        out = []
+        j = self.index(gid)
+        while j >= 0:
+            out.append(self.rows[j])
+            p = int(self.rows["parent_id"][j])
+            j = self.index(p) if p > 0 else -1
+        return np.array(out, dtype=capi.LINEAGE_ROW_DTYPE)
+
+
 class Genotype:
     """One active genotype, read through the arbiter's arrays.  The object
     for a key stays the same while the genotype lives; after its removal it
@@ -242,8 +361,9 @@ class GenotypeArbiter:
     those that cross the threshold (names) and for Genotype objects a caller
     asked for."""
 
-    def __init__(self, threshold=3):
+    def __init__(self, threshold=3, lineage=False):
         self.threshold = threshold
+        self.lineage = LineageStore() if lineage else None
         self.keys = np.zeros(0, dtype=np.uint64)
         self.ids = np.zeros(0, dtype=np.int64)
         self.lengths = np.zeros(0, dtype=np.int32)
@@ -274,9 +394,15 @@ class GenotypeArbiter:
         self.sz_count[size] = k + 1
         return k + 1
 
-    def update_table(self, table, totals, update):
+    def update_table(self, table, totals, update, parent_keys=None, sequences=None, generations=None):
         """Classify one genotype table (capi.GENOTYPE_DTYPE rows, keys
-        ascending; table_from_census or capi.get_genotypes)."""
+        ascending; table_from_census or capi.get_genotypes).  With lineage on,
+        per table row: parent_keys = the parent key of its first cell
+        (avgpu_get_parent_keys), sequences = that cell's tape prefix of
+        birth_len sites as canonical codes (or None), generations = its census
+        generation; only the new genotypes' entries are read."""
+        if self.lineage is not None and parent_keys is None:
+            raise ValueError("lineage is on: update_table needs the table rows' parent keys")
         tk = table["genotype_key"]
         m, old = len(tk), len(self.keys)
         pos = np.searchsorted(self.keys, tk)
@@ -286,6 +412,11 @@ class GenotypeArbiter:
         dst = np.flatnonzero(found)
         src = pos[dst]
         fresh = np.flatnonzero(~found)
+        old_keys, old_ids = self.keys, self.ids
+        if self.lineage is not None and len(src) < old:
+            gone = np.ones(old, dtype=bool)
+            gone[src] = False
+            self.lineage.deactivate(np.sort(old_ids[gone]), update)
         if self._views and len(src) < old:            # genotypes that disappear
             gone = np.ones(old, dtype=bool)
             gone[src] = False
@@ -306,6 +437,11 @@ class GenotypeArbiter:
         by_cell = fresh[np.argsort(table["first_cell"][fresh], kind="stable")]
         ids[by_cell] = self.next_id + np.arange(len(fresh))
         lengths[fresh] = table["genome_length"][fresh]
+        if self.lineage is not None and len(fresh):
+            self.lineage.append([(int(tk[j]), int(ids[j]), int(parent_keys[j]), int(lengths[j]),
+                                  int(generations[j]) if generations is not None else 0,
+                                  sequences[j] if sequences is not None else None) for j in by_cell],
+                                old_keys, old_ids, update)
         self.next_id += len(fresh)
         self.tot_genotypes += len(fresh)
         total += np.maximum(0, units - prev)
@@ -359,6 +495,24 @@ class GenotypeArbiter:
     def best(self):
         return self.dominant()
 
+    # ---- ancestry (lineage=True) ----
+    def _store(self):
+        if self.lineage is None:
+            raise ValueError("this arbiter keeps no lineage (GenotypeArbiter(threshold, lineage=True))")
+        return self.lineage
+
+    def prune(self):
+        """drop the dead genotypes without a living descendant; returns how many"""
+        return self._store().prune()
+
+    def lineage_of(self, gid):
+        """the store's rows from genotype `gid` up to its root"""
+        return self._store().lineage_of(gid)
+
+    def depth_of(self, gid):
+        j = self._store().index(gid)
+        return int(self.lineage.rows["depth"][j]) if j >= 0 else 0
+
     def genotype_averages(self, g):
         """(merit, gestation, fitness, repro rate, copied size, max fitness)
         over g's organisms with a completed gestation: the table's sums over
@@ -377,10 +531,40 @@ class GenotypeArbiter:
         if g is None:
             return None
         merit, gest, fit, repro, copied, maxfit = self.genotype_averages(g)
-        # births / breed true / depth / breed in need lineage records: 0
+        # births / breed true / breed in need per-genotype birth records: 0;
+        # the depth comes from the lineage store where one is kept
+        depth = self.depth_of(g.id) if self.lineage is not None else 0
         return [update, merit, gest, fit, repro, g.length, copied, 0.0, g.num_units,
-                0, 0, 0, 0, maxfit, g.id, g.name]
+                0, 0, depth, 0, maxfit, g.id, g.name]
 
+
+def classify_with_lineage(arbiter, world, update, handlers, cap=capi.MAX_GENOME):
+    """One classification of `world` by a host GenotypeArbiter(lineage=True),
+    the specification run beside a device store to check it (it drags the
+    parent-key row and a census to the host: not a production path; the
+    device keeps the store itself, DeviceGenotypeArbiter(lineage=True)).
+    Fed from the device: the genotype table (world.genotypes), the parent key
+    and census generation of each row's first cell (world.parent_keys,
+    world.census) and, for the new genotypes only, that cell's tape prefix of
+    birth_length sites as canonical codes (world.states; `handlers` =
+    InstSet.handlers, op -> canonical code).  A world without parent_keys (the
+    oracle backend keeps no ancestry) raises."""
+    if not hasattr(world, "parent_keys"):
+        raise ValueError("lineage needs a world that records parent keys (avgpu_get_parent_keys): "
+                         f"{type(world).__name__} has none")
+    table, totals = world.genotypes() if hasattr(world, "genotypes") else table_from_census(world.census())
+    first = table["first_cell"]
+    pk = world.parent_keys()[first]
+    gens = world.census()["generation"][first]
+    tk = table["genotype_key"]
+    old = len(arbiter.keys)
+    pos = np.minimum(np.searchsorted(arbiter.keys, tk), max(old - 1, 0))
+    known = arbiter.keys[pos] == tk if old else np.zeros(len(tk), dtype=bool)
+    seqs = [None] * len(tk)
+    for j in np.flatnonzero(~known):
+        st, ops, _ = world.states(int(first[j]), 1, cap)
+        seqs[j] = bytes(handlers[x] for x in ops[:min(st[0].birth_length, cap)])
+    arbiter.update_table(table, totals, update, parent_keys=pk, sequences=seqs, generations=gens)
 
 
 class GenotypeSnapshot:
@@ -436,8 +620,10 @@ class DeviceGenotypeArbiter:
 
     census = None             # never fed a census
 
-    def __init__(self, threshold=3):
+    def __init__(self, threshold=3, lineage=False):
         self.threshold = threshold
+        self.lineage = bool(lineage) or None     # (dominant_row: None = no depth column)
+        self._lin = None
         self.active = _DeviceActive(self)
         self.world = None
         self.summary = np.zeros(1, dtype=capi.ARBITER_SUMMARY_DTYPE)[0]
@@ -448,6 +634,7 @@ class DeviceGenotypeArbiter:
     def _drop(self):
         self._generation += 1
         self._state = None
+        self._lin = None
         self._views = {}
         self._dominant = None
         self.cell_order = self.cell_bounds = None
@@ -457,7 +644,43 @@ class DeviceGenotypeArbiter:
         self.world = world
         self.summary = world.classify_genotypes(update, self.threshold)
         self._drop()
+        if self.lineage:                         # prune when the store exceeds twice the active rows
+            s = world.lineage_state(summary_only=True)[2]
+            if int(s["rows"]) > 2 * int(s["active_rows"]):
+                world.prune_lineage()
         return self.summary
+
+    # ---- ancestry: the device store (lineage=True), fetched lazily ----
+    def enable(self, world, rows_hint=0, arena_hint=0):
+        """turn the world's store on (a new world, or after avgpu_reset_arbiter)"""
+        self.world = world
+        world.enable_lineage(True, rows_hint, arena_hint)
+
+    def lineage_store(self):
+        """the store as a host LineageStore (one avgpu_get_lineage, cached
+        until the next classify)"""
+        if not self.lineage or self.world is None:
+            raise ValueError("this arbiter keeps no lineage (DeviceGenotypeArbiter(threshold, lineage=True))")
+        if self._lin is None:
+            rows, arena, s = self.world.lineage_state()
+            st = LineageStore()
+            st.rows, st.arena = rows, bytearray(arena.tobytes())
+            st.num_orphans, st.num_unsequenced = int(s["num_orphans"]), int(s["num_unsequenced"])
+            st.dropped_last_prune = int(s["dropped_last_prune"])
+            self._lin = st
+        return self._lin
+
+    def lineage_of(self, gid):
+        return self.lineage_store().lineage_of(gid)
+
+    def depth_of(self, gid):
+        st = self.lineage_store()
+        j = st.index(gid)
+        return int(st.rows["depth"][j]) if j >= 0 else 0
+
+    def prune(self):
+        self._lin = None
+        return int(self.world.prune_lineage()["dropped_last_prune"])
 
     def attach(self, world):
         """take over the state `world` holds (after a restore)"""

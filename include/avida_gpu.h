@@ -713,6 +713,69 @@ int avgpu_state_digests(avgpu_world* w, int64_t first_cell, int64_t count, uint6
  * copied into its own sites; a checkpoint carries the keys and sets them
  * after avgpu_set_states (avida_amd/checkpoint.py). */
 int avgpu_set_genotype_keys(avgpu_world* w, int64_t first_cell, int64_t count, const uint64_t* keys);
+/* ---- the lineage store ----
+ * One genotype ever classified (what Systematics::Genotype keeps of its
+ * ancestry, systematics/Genotype.cc:139-176): rows ascend by id. */
+typedef struct avgpu_lineage_row {
+  uint64_t genotype_key;
+  int64_t id;
+  int64_t parent_id;            /* 0: injected; -1: orphan (the parent's genotype was never classified) */
+  int64_t seq_off;              /* offset of the captured birth genome in the arena; -1: not captured */
+  int64_t update_born;
+  int64_t update_deactivated;   /* -1 while active */
+  int32_t depth, genome_length, gen_born, reserved;
+} avgpu_lineage_row;
+typedef struct avgpu_lineage_summary {
+  int64_t rows, active_rows, arena_bytes;
+  int64_t num_orphans, num_unsequenced;   /* cumulative */
+  int64_t max_depth;                      /* over the rows held */
+  int64_t dropped_last_prune;
+  int64_t reserved;
+} avgpu_lineage_summary;
+/* Turn the store on or off (replaces the bookkeeping Genotype's constructor
+ * and GenotypeArbiter::removeGenotype do per birth and death,
+ * systematics/Genotype.cc:139-176, GenotypeArbiter.cc:499-530).  Allowed only
+ * while the arbiter state is empty (a new world, or right after
+ * avgpu_reset_arbiter), else AVGPU_ESTATE.  While on, every
+ * avgpu_classify_genotypes also maintains the store; avgpu_reset_arbiter
+ * empties it.  rows_hint / arena_hint: the first buffer sizes (0: defaults);
+ * buffers grow by 1.25x.  AVGPU_EUNSUPPORTED on a strip tile. */
+int avgpu_enable_lineage(avgpu_world* w, int on, int64_t rows_hint, int64_t arena_hint);
+/* The store into host memory (replaces walking Genotype::Parents(),
+ * systematics/Genotype.h): with NULL buffers only the summary; a buffer that
+ * is too small gives AVGPU_EINVAL with nothing written.  Returns the rows. */
+int avgpu_get_lineage(avgpu_world* w, avgpu_lineage_row* rows, int64_t cap, uint8_t* genomes, int64_t genome_cap,
+                      avgpu_lineage_summary* summary);
+/* Resume (the historic genotypes a saved population carries,
+ * main/cPopulation.cc:6490): after avgpu_set_arbiter.  Validates strictly
+ * ascending ids, parent_id < id, parents present or <= 0, offsets inside the
+ * genomes, and every active arbiter id present as an active row; on a
+ * violation AVGPU_EINVAL with the state unchanged. */
+int avgpu_set_lineage(avgpu_world* w, int64_t n, const avgpu_lineage_row* rows, const uint8_t* genomes, int64_t bytes,
+                      const avgpu_lineage_summary* summary);
+/* Drop the dead genotypes without a living descendant (the passive references
+ * of systematics/Genotype.cc:159, GenotypeArbiter.cc:499-530): a row stays iff
+ * it is active or lies on the parent_id chain of an active row; rows and arena
+ * are compacted stably. */
+int avgpu_prune_lineage(avgpu_world* w, avgpu_lineage_summary* summary);
+/* Device time (no reference equivalent) of the last classification's lineage
+ * part and of the last prune, in ms. */
+int avgpu_last_lineage_ms(avgpu_world* w, double* classify_ms, double* prune_ms);
+
+/* Ancestry (replaces the parent pointer Systematics::Genotype keeps,
+ * systematics/Genotype.cc:139-176, as far as the hot path goes): the parent
+ * key of cells first .. first+count-1 into host memory -- the genotype key
+ * (avgpu_get_census) of the parent's cell at the moment of the divide that
+ * placed the organism, i.e. the key of the parent's birth genome, taken
+ * before any activation of that step.  0 for an organism that avgpu_set_org(s)
+ * / avgpu_set_states put there and for a dead cell.  Stream-ordered behind
+ * queued updates; complete on return. */
+int avgpu_get_parent_keys(avgpu_world* w, int64_t first_cell, int64_t count, uint64_t* out);
+/* checkpoint / resume (the parent ids a saved population carries,
+ * main/cPopulation.cc:6490-6560): the parent keys of cells first ..
+ * first+count-1, set after avgpu_set_states (which clears them).  Also a test
+ * hook, as avgpu_set_genotype_keys. */
+int avgpu_set_parent_keys(avgpu_world* w, int64_t first_cell, int64_t count, const uint64_t* keys);
 /* checkpoint / resume: the inverse of avgpu_get_states -- cells first ..
  * first+count-1 take states[i] and their tapes from mem_ops / mem_flags
  * (instruction-set op codes; flags bit0 copied, bit2 executed), mem_cap bytes

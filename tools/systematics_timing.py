@@ -21,7 +21,14 @@ text table (device ms, bytes to the host, wall ms of the systematics step).
 
 The update itself is timed the same way (queued run_update + sync, wall).
 
-    python tools/systematics_timing.py [--root DIR] [--updates 20] [--side 1024]
+With --lineage the script measures the lineage store instead:
+the store is turned on before the first classification, every update is
+classified on the device, and per update it reports the device ms of the
+arbiter (avgpu_last_arbiter_ms: the classification without the store) and of
+the store's part (avgpu_last_lineage_ms), the rows appended and the store's
+size; after the last update one prune, with its device ms and what it keeps.
+
+    python tools/systematics_timing.py [--root DIR] [--updates 20] [--side 1024] [--lineage]
 """
 import argparse
 import ctypes as C
@@ -40,6 +47,7 @@ def main():
     ap.add_argument("--burn-in", type=int, default=None)
     ap.add_argument("--seed", type=int, default=101)
     ap.add_argument("--table", default=None, help="write the routes' means as a text table to this file")
+    ap.add_argument("--lineage", action="store_true", help="measure the lineage store (DESIGN.md 10.6)")
     a = ap.parse_args()
     root = os.path.abspath(a.root)
     sys.path.insert(0, root)
@@ -55,6 +63,10 @@ def main():
     for _ in range(burn):
         capi.check(lib, lib.avgpu_run_update(h, None))
     capi.check(lib, lib.avgpu_sync(h))
+    if a.lineage:
+        lineage_timing(a, lib, capi, h, n, burn)
+        lib.avgpu_destroy(h)
+        return
     table_path = hasattr(capi, "get_genotypes")
     arb = systematics.GenotypeArbiter()
     device_path = table_path and hasattr(lib, "avgpu_classify_genotypes")
@@ -173,6 +185,67 @@ def main():
         with open(a.table, "w") as f:
             f.write("\n".join(lines) + "\n")
     lib.avgpu_destroy(h)
+
+
+def lineage_timing(a, lib, capi, h, n, burn):
+    capi.enable_lineage(lib, h, True)
+    rows = []
+    for u in range(a.updates + 1):            # row 0: every genotype is new, the buffers are allocated
+        t0 = time.perf_counter()
+        capi.check(lib, lib.avgpu_run_update(h, None))
+        capi.check(lib, lib.avgpu_sync(h))
+        t1 = time.perf_counter()
+        s = capi.classify_genotypes(lib, h, burn + u, 3)
+        t2 = time.perf_counter()
+        ams, nb, lms, pms = C.c_double(), C.c_int64(), C.c_double(), C.c_double()
+        capi.check(lib, lib.avgpu_last_arbiter_ms(h, C.byref(ams), C.byref(nb)))
+        capi.check(lib, lib.avgpu_last_lineage_ms(h, C.byref(lms), C.byref(pms)))
+        ls = capi.get_lineage(lib, h, summary_only=True)[2]
+        r = {"update": burn + u, "update_ms": 1e3 * (t1 - t0), "classify_wall_ms": 1e3 * (t2 - t1),
+             "arbiter_device_ms": ams.value, "lineage_device_ms": lms.value, "genotypes": int(s["num_genotypes"]),
+             "rows_appended": int(s["num_new"]), "store_rows": int(ls["rows"]), "arena_bytes": int(ls["arena_bytes"]),
+             "num_unsequenced": int(ls["num_unsequenced"]), "num_orphans": int(ls["num_orphans"]),
+             "max_depth": int(ls["max_depth"])}
+        rows.append(r)
+        print(json.dumps(r), flush=True)
+    before = rows[-1]
+    t0 = time.perf_counter()
+    ps = capi.prune_lineage(lib, h)
+    t1 = time.perf_counter()
+    lms, pms = C.c_double(), C.c_double()
+    capi.check(lib, lib.avgpu_last_lineage_ms(h, C.byref(lms), C.byref(pms)))
+    steady = rows[1:]
+    mean = lambda k: sum(x[k] for x in steady) / len(steady)     # noqa: E731
+    out = {"cells": n, "updates": len(steady), "mean": {k: mean(k) for k in steady[0] if k != "update"},
+           "prune": {"update": before["update"], "device_ms": pms.value, "wall_ms": 1e3 * (t1 - t0),
+                     "rows_before": before["store_rows"], "rows_kept": int(ps["rows"]),
+                     "active_rows": int(ps["active_rows"]), "dropped": int(ps["dropped_last_prune"]),
+                     "arena_bytes_before": before["arena_bytes"], "arena_bytes_kept": int(ps["arena_bytes"])}}
+    print(json.dumps(out), flush=True)
+    if a.table:
+        m, p = out["mean"], out["prune"]
+        lines = ["# tools/systematics_timing.py --lineage --side %d: %d updates after %d burn-in updates, %d cells"
+                 % (a.side, len(steady), burn, n),
+                 "# per-update means: %.0f genotypes, %.0f rows appended; device ms: arbiter %.3f, lineage part %.3f "
+                 "(classification with the store %.3f); wall ms of the classification %.3f; the update itself %.3f"
+                 % (m["genotypes"], m["rows_appended"], m["arbiter_device_ms"], m["lineage_device_ms"],
+                    m["arbiter_device_ms"] + m["lineage_device_ms"], m["classify_wall_ms"], m["update_ms"]),
+                 "# first classification (update %d, %d rows appended): arbiter %.3f ms, lineage part %.3f ms device"
+                 % (rows[0]["update"], rows[0]["rows_appended"], rows[0]["arbiter_device_ms"],
+                    rows[0]["lineage_device_ms"]),
+                 "# prune after update %d: %.3f ms device (%.3f ms wall); rows %d -> %d (%d active, %d dropped); "
+                 "arena bytes %d -> %d" % (p["update"], p["device_ms"], p["wall_ms"], p["rows_before"], p["rows_kept"],
+                                           p["active_rows"], p["dropped"], p["arena_bytes_before"],
+                                           p["arena_bytes_kept"]),
+                 "# store at the last update: %d unsequenced, %d orphans, largest depth %d"
+                 % (before["num_unsequenced"], before["num_orphans"], before["max_depth"]),
+                 "#", "# per update: update, genotypes, rows appended, store rows, arena bytes, arbiter device ms, "
+                 "lineage device ms, classification wall ms"]
+        lines += ["%d %d %d %d %d %.3f %.3f %.3f" % (x["update"], x["genotypes"], x["rows_appended"], x["store_rows"],
+                                                    x["arena_bytes"], x["arbiter_device_ms"], x["lineage_device_ms"],
+                                                    x["classify_wall_ms"]) for x in rows]
+        with open(a.table, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
