@@ -12,7 +12,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["interp.hip", "world.hip", "resources.hip", "genotypes.hip", "arbiter.hip", "lineage.hip", "landscape.hip",
+SOURCES = ["interp.hip",
+           # the kernels around k_interpret, one file per subsystem (csrc/births.h is what they share)
+           "state.hip", "sched.hip", "place.hip", "activate.hip", "stats.hip",
+           "resources.hip", "genotypes.hip", "arbiter.hip", "lineage.hip", "landscape.hip",
            # the host side of the C ABI, one file per subsystem (csrc/host.h is what they share)
            "capi.hip", "capi_serial.hip", "capi_systematics.hip", "capi_state.hip", "capi_landscape.hip",
            "capi_resources.hip", "capi_tiles.hip"]

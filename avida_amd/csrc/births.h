@@ -1,6 +1,7 @@
-// births.h -- offspring helpers shared by the placement kernels (world.hip)
-// and the serial world (interp.hip): the neighbourhood, the divide-mutation
-// edits, and ActivateOrganism / SetupOffspring of a record into a cell.
+// births.h -- offspring helpers shared by placement (place.hip), activation
+// (activate.hip) and the serial world (interp.hip): the neighbourhood, the
+// divide-mutation edits, ActivateOrganism / SetupOffspring of a record into a
+// cell, and a birth record's placement row, states and claim keys.
 // Paths are relative to avida-core/source/ of the reference.
 #pragma once
 #include "device.h"
@@ -375,6 +376,104 @@ __device__ __forceinline__ Child child_of_record(const DevWorld& W, int64_t i) {
   const int4* row = reinterpret_cast<const int4*>(W.b_inh + i * BI_WORDS);
   const int4 q0 = row[0], q1 = row[1], q2 = row[2], q6 = row[BI_PARENT / 4];   // 16-B loads of the record's row
   return child_of_row(W, i, q0, q1, q2, q6);
+}
+
+// ---- what placement (place.hip) and activation (activate.hip) share ----
+// A queued birth's record row in registers, its placement states and claim
+// keys, the walk over the birth queue, a strip's edge and ghost rows.
+
+// -- the record's row --
+// The words of a record's row that placement works with, in registers: a
+// placement kernel loads them (three quads, all in flight together) before
+// it tests anything, and passes on what it changed instead of loading it back.
+struct PlaceRow {
+  uint32_t lo, hi, ctr, fin;        // BI_RLO, BI_RHI, BI_RCTR, BI_FINAL
+  int parent;
+  uint32_t seq;
+  int len, state, target;           // BI_PARENT .. BI_TARGET
+  unsigned long long prio;          // BI_PRIO
+};
+__device__ __forceinline__ PlaceRow place_row(const DevWorld& W, int64_t r) {
+  static_assert(BI_RLO == 8 && BI_RHI == 9 && BI_RCTR == 10 && BI_FINAL == 11 && BI_PARENT == 24 && BI_SEQ == 25 &&
+                BI_LEN == 26 && BI_STATE == 27 && BI_TARGET == 28 && BI_PRIO == 30, "row quads");
+  const int4* q = reinterpret_cast<const int4*>(W.b_inh + r * BI_WORDS);
+  const int4 q2 = q[2], q6 = q[6], q7 = q[7];
+  PlaceRow p;
+  p.lo = (uint32_t)q2.x; p.hi = (uint32_t)q2.y; p.ctr = (uint32_t)q2.z; p.fin = (uint32_t)q2.w;
+  p.parent = q6.x; p.seq = (uint32_t)q6.y; p.len = q6.z; p.state = q6.w;
+  p.target = q7.x;
+  p.prio = (unsigned long long)(uint32_t)q7.z | ((unsigned long long)(uint32_t)q7.w << 32);
+  return p;
+}
+__device__ __forceinline__ void set_state(const DevWorld& W, int64_t r, int st) {
+  W.b_inh[r * BI_WORDS + BI_STATE] = st;
+}
+
+// -- time-ordered placement (oracle/oracle.cc "3. Time-ordered placement";
+// DESIGN.md 5): claim keys and record states --
+// claim key: [63:48] time key (kill: t, empty: 0xFFFF - t), [47] kill,
+// [46:32] the pick's draw >> 17, [31:8] the parent's GLOBAL cell id (tiles
+// agree), [7:0] its divide number
+__device__ __forceinline__ unsigned long long claim_key(uint32_t t, bool kill, uint32_t draw, int64_t gparent,
+                                                        uint32_t seq) {
+  const unsigned long long tk = kill ? (unsigned long long)(t & 0xFFFFu) : (unsigned long long)(0xFFFFu - (t & 0xFFFFu));
+  return (tk << 48) | ((unsigned long long)(kill ? 1 : 0) << 47) | ((unsigned long long)(draw >> 17) << 32) |
+         ((unsigned long long)(gparent & 0xFFFFFF) << 8) | (unsigned long long)(seq & 0xFF);
+}
+__device__ __forceinline__ bool key_kill(unsigned long long k) { return ((k >> 47) & 1ull) != 0ull; }
+__device__ __forceinline__ uint32_t key_time(unsigned long long k) {
+  const uint32_t tk = (uint32_t)(k >> 48);
+  return key_kill(k) ? tk : 0xFFFFu - tk;
+}
+// record states (the row's BI_STATE word)
+enum : int8_t { BS_PENDING = 0, BS_WON = 1 /* 1 + round */, BS_KILL_LOST = 8 /* 8 + round */,
+                BS_CANCELLED = -1, BS_NO_CELL = -2 /* - round: found no cell in that round */ };
+__device__ __forceinline__ uint32_t rec_time(const DevWorld& W, int64_t r) {
+  return BI_TIME(W.b_inh[r * BI_WORDS + BI_FINAL]);
+}
+__device__ __forceinline__ uint32_t owner_time(const DevWorld& W, int o) {
+  return o >= 0 ? rec_time(W, o) : (uint32_t)((-2 - o) >> 2);
+}
+// a round's winner with time t takes its cell unless the cell's owner from an
+// earlier round is later in time (that owner overwrote it)
+__device__ __forceinline__ bool takes_cell(const DevWorld& W, int owner, uint32_t t) {
+  return owner == -1 || owner_time(W, owner) <= t;
+}
+// the last round a record claimed in (-1: none) -- its claims are cleared at
+// activation (round k's at b_tgt[k])
+__device__ __forceinline__ int last_claim_round(int st) {
+  if (st == BS_PENDING) return 3;
+  if (st >= BS_WON && st < BS_WON + 4) return st - BS_WON;
+  if (st >= BS_KILL_LOST && st < BS_KILL_LOST + 4) return st - BS_KILL_LOST;
+  if (st <= BS_NO_CELL) return BS_NO_CELL - st - 1;
+  return -1;
+}
+
+// -- the walk over the birth queue --
+// grid-stride over the birth queue (its length is only known on the device)
+// with the lane's record id r of entry i.  The list entry is loaded ahead:
+// b_list[i]'s address needs neither of the queue's lengths, so it is issued
+// together with them instead of a round trip behind them (queue_len ->
+// rec_of); an entry past the primary records reads a clamped slot that is
+// not used.
+__device__ __forceinline__ int list_entry(const DevWorld& W, int64_t i) { return W.b_list[i < W.n ? i : W.n - 1]; }
+__device__ __forceinline__ int64_t rec_from(const DevWorld& W, int64_t i, int64_t p, int64_t e) {
+  return i < p ? e : W.n + (i - p);
+}
+#define QUEUE_RECS(i, r, first, stride) \
+  for (int64_t i = (first), _qs = (stride), _e = list_entry(W, i), _p = W.b_count[BQ_PRIMARY], \
+               _qn = queue_len(W), r = rec_from(W, i, _p, _e); \
+       i < _qn; i += _qs, _e = i < _qn ? list_entry(W, i) : 0, r = rec_from(W, i, _p, _e))
+#define QUEUE_LOOP(i, r) \
+  QUEUE_RECS(i, r, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x)
+
+// -- strip tiles' halo rows (DESIGN.md "Multi-GPU") --
+// Edge rows: top = local row 0, bottom = local row rows-1; ghost rows after n.
+__device__ __forceinline__ int64_t edge_cell(const DevWorld& W, int d, int x) {
+  return d == 0 ? (int64_t)x : (int64_t)(W.rows - 1) * W.world_x + x;
+}
+__device__ __forceinline__ int64_t ghost_cell(const DevWorld& W, int d, int x) {
+  return W.n + (int64_t)d * W.world_x + x;
 }
 
 }  // namespace

@@ -8,7 +8,8 @@
 // birth queue, scratch) on one HIP device and one HIP stream.  Each entry
 // point names the reference interface it replaces in the header.  There is no
 // CPU execution path in this library: every state transition of the hot path
-// runs in the kernels of interp.hip / world.hip.
+// runs in the kernels of interp.hip and of state.hip, sched.hip, place.hip,
+// activate.hip and stats.hip around it.
 #include "host.h"
 
 using namespace avh;

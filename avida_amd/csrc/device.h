@@ -21,11 +21,11 @@
 // copied size, executed size, gestation time, the offspring's RNG key and
 // counter, the parent's last task counts; then the record's placement state
 // (words 24..31: its parent's cell, the parent's divide number, the offspring's
-// length after the divide mutations, its BS_* state (world.hip), its target of
+// length after the divide mutations, its BS_* state (births.h), its target of
 // the current round and that round's claim key, 8-B aligned) -- everything a
 // placement kernel needs of a record is in the row it loads first
 // (BI_FINAL bit 0 = 1: the divide left the offspring's fitness and key and the
-// parent's phenotype to finalize_key / finalize_phenotype, world.hip; bits
+// parent's phenotype to finalize_key / finalize_phenotype, place.hip; bits
 // 16..31 the offspring's birth time in the update, 1/2^16 -- DESIGN.md 5)
 enum { BI_MERIT = 0, BI_FITNESS = 2, BI_GEN = 4, BI_CCOPIED = 5, BI_EXEC = 6, BI_GEST = 7,
        BI_RLO = 8, BI_RHI = 9, BI_RCTR = 10, BI_FINAL = 11, BI_LTASK = 12,
@@ -322,7 +322,7 @@ struct DevWorld {
   // halo buffers per direction d (0: tile above, 1: tile below), registered by
   // the host: halo_bytes(X) = per round parity X u64 claims on the receiver's
   // edge row and X u64 the sender's own claims on its edge row, then X u8
-  // edge-row occupancy (world.hip halo_cl / halo_occ)
+  // edge-row occupancy (place.hip halo_cl / halo_occ)
   uint8_t* h_send[2];
   uint8_t* h_recv[2];
   // birth-record buffers per direction: HaloHdr, X HaloRec, arena of r_arena bytes
@@ -485,7 +485,7 @@ enum {
   RESET_COUNTS = 1,   // the update's counters, the birth-queue and class-list lengths
   RESET_QUEUES = 2    // a later step of the update: the queue and list lengths only
 };
-// k_block_counts' `mode` (world.hip): where the tree's leaves and the totals come from
+// k_block_counts' `mode` (sched.hip): where the tree's leaves and the totals come from
 enum {
   BC_OWN = 0,         // this world's partials and totals
   BC_GATHERED = 1,    // a strip: every strip's gathered partials vectors
@@ -933,14 +933,15 @@ static inline int env_int(const char* name, int dflt, int lo, int hi) {
   const int v = e ? atoi(e) : dflt;
   return (v >= lo && v <= hi) ? v : dflt;
 }
+// the blocks of b threads that cover n items
+static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
+// ---- interp.hip ----
 // class 0 runs densely over cells [first, first+count); classes 1..3 over their lists
 // after_class[k] (optional): event recorded after the class-k launch
 // dW: device copy of W (avgpu_world::push_world)
 // sorted: a world update's main pass (class 0 follows k_window_order's windows)
 void launch_serial_update(const DevWorld& W, const DevWorld* dW, hipStream_t s);
-void launch_serial_post(const DevWorld& W, hipStream_t s, double* stats);
-void launch_reset_counts(const DevWorld& W, hipStream_t s);
 void launch_interpret_classes(const DevWorld& W, const DevWorld* dW, int mode, hipStream_t s,
                               int64_t first, int64_t count, int* launches,
                               hipEvent_t* after_class = nullptr, bool sorted = false);
@@ -951,7 +952,27 @@ void launch_interpret_classes(const DevWorld& W, const DevWorld* dW, int mode, h
 // last of them), then one bucket for the window's cells that are not class 0
 #define SORT_BUCKETS 258
 bool class_timing_all();   // AVGPU_CLASS_TIMING (interp.hip)
+// the newborn pass of a batch step: the organisms k_activate listed
+void launch_newborns(const DevWorld& W, const DevWorld* dW, hipStream_t s);
+
+// ---- state.hip: organisms and their state in and out ----
+void launch_classify_uniform(const DevWorld& W, hipStream_t s, int64_t first, int64_t count,
+                             const int32_t* d_budget, int32_t uniform);
+void launch_set_orgs(const DevWorld& W, hipStream_t s, int64_t first, int64_t count,
+                     const uint8_t* d_codes, const int32_t* d_offsets, const int32_t* d_lens,
+                     const double* d_merits, const int32_t* d_inputs, int deterministic);
+void launch_get_states(const DevWorld& W, hipStream_t s, int64_t first, int64_t count,
+                       avgpu_cpu_state* d_states, uint8_t* d_codes, int cap);
+void launch_set_states(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, const avgpu_cpu_state* in,
+                       const uint8_t* codes, int cap);
+void launch_state_digest(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, uint64_t* d_out);
+void launch_get_census(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, avgpu_census* d_out);
+void launch_get_parent_keys(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, uint64_t* d_out);
+
+// ---- sched.hip: the merit total, the scheduler tree, the allotment ----
+void launch_reset_counts(const DevWorld& W, hipStream_t s);
 void launch_age_tick(const DevWorld& W, hipStream_t s);
+void launch_merit_total(const DevWorld& W, hipStream_t s, double* d_totals, double* d_scratch);
 // sub-update `sub` of `nsub` (avgpu_cfg.sub_updates): the
 // resources step and the update's counters are reset at sub 0 only; the key
 // of the scheduler's node draws is update x nsub + sub (the caller's `update`)
@@ -965,17 +986,33 @@ void launch_world_begin(const DevWorld& W, hipStream_t s, double* d_totals, doub
 __host__ __device__ __forceinline__ long long sub_share(long long n, int s, int K) {
   return K == 1 ? n : (n * (s + 1)) / K - (n * s) / K;
 }
+// strip tiles: the partials every strip gathers, then the tree over them
+void launch_tile_partials(const DevWorld& W, hipStream_t s, double* d_out, int reset);
 void launch_tile_pre(const DevWorld& W, hipStream_t s, const double* d_gathered, int ntiles, double* d_totals,
                      uint32_t update, int sub = 0, int nsub = 1);
 // allotment draw of organism (lo, hi) in update u (oracle allot_draw)
 __device__ __forceinline__ uint32_t allot_draw(uint32_t lo, uint32_t hi, uint32_t update) {
   return lowbias32(lowbias32(update * 0x85EBCA6BU + hi) ^ lo ^ 0x27D4EB2FU);
 }
+
+// ---- resources.hip ----
 void launch_resources_begin(const DevWorld& W, hipStream_t s);
 void launch_resources_end(const DevWorld& W, hipStream_t s);
 void launch_resources_pack(const DevWorld& W, hipStream_t s);
 bool res_stepped(const DevWorld& W);   // launch_resources_begin wrote res_amount_alt
 void launch_resources_settle(const DevWorld& W, hipStream_t s, const unsigned long long* sum);
+
+// ---- activate.hip: the placed births into their cells, the halo records ----
+// fused: ACT_WORLD / ACT_STRIP; key, sub, nsub: the batch step's scheduler key and share
+void launch_activate(const DevWorld& W, hipStream_t s, int fused, uint32_t key, int sub, int nsub);
+void launch_halo_pack(const DevWorld& W, hipStream_t s);
+void launch_activate_remote(const DevWorld& W, hipStream_t s, uint32_t key, int sub, int nsub);
+
+// ---- stats.hip ----
+// the update's statistics into d_stats (k_stats_partial + k_stats_final)
+void launch_stats(const DevWorld& W, hipStream_t s, double* d_stats);
+
+// ---- place.hip: placement, and the order of a step after interpretation ----
 // placement and activation of batch step `sub` of `nsub` (key: its scheduler
 // key), the newborns listed for the newborn pass; then launch_world_end
 // pred_out (coherent mapped host memory, the update's last step): the
@@ -983,22 +1020,12 @@ void launch_resources_settle(const DevWorld& W, hipStream_t s, const unsigned lo
 void launch_world_post(const DevWorld& W, hipStream_t s, uint32_t key, int sub, int nsub,
                        long long* pred_out = nullptr, long long pred_seq = 0);
 void launch_world_end(const DevWorld& W, hipStream_t s, double* d_stats, bool eager);
-// the newborn pass of a batch step (interp.hip): the organisms k_activate listed
-void launch_newborns(const DevWorld& W, const DevWorld* dW, hipStream_t s);
-// the update's statistics into d_stats (k_stats_partial + k_stats_final)
-void launch_stats(const DevWorld& W, hipStream_t s, double* d_stats);
-void launch_classify_uniform(const DevWorld& W, hipStream_t s, int64_t first, int64_t count,
-                             const int32_t* d_budget, int32_t uniform);
-void launch_set_orgs(const DevWorld& W, hipStream_t s, int64_t first, int64_t count,
-                     const uint8_t* d_codes, const int32_t* d_offsets, const int32_t* d_lens,
-                     const double* d_merits, const int32_t* d_inputs, int deterministic);
-void launch_get_states(const DevWorld& W, hipStream_t s, int64_t first, int64_t count,
-                       avgpu_cpu_state* d_states, uint8_t* d_codes, int cap);
-void launch_set_states(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, const avgpu_cpu_state* in,
-                       const uint8_t* codes, int cap);
-void launch_state_digest(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, uint64_t* d_out);
-void launch_get_census(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, avgpu_census* d_out);
-void launch_get_parent_keys(const DevWorld& W, hipStream_t s, int64_t first, int64_t count, uint64_t* d_out);
+void launch_serial_post(const DevWorld& W, hipStream_t s, double* stats);
+// strip tiles
+void launch_tile_after_interpret(const DevWorld& W, hipStream_t s);
+void launch_tile_place(const DevWorld& W, hipStream_t s, int round, int phase, uint32_t key, int sub, int nsub);
+void launch_tile_finish(const DevWorld& W, hipStream_t s, uint32_t key, int sub, int nsub);
+
 // the genotype table (genotypes.hip).  GtAgg: what a run of
 // sorted positions of one genome key adds up to; GtScratch: the world's
 // scratch for the grouping, allocated at the first avgpu_get_genotypes.
@@ -1168,9 +1195,3 @@ void launch_land_rows(const LandScratch& S, hipStream_t s, int distance);
 // the pair mutants' tiles [t0, t1) against S.chart, and their rows
 void launch_land_epi_reduce(const LandScratch& S, hipStream_t s, int64_t m0, int64_t t0, int64_t t1);
 void launch_land_epi_rows(const LandScratch& S, hipStream_t s);
-void launch_merit_total(const DevWorld& W, hipStream_t s, double* d_totals, double* d_scratch);
-// strip tiles
-void launch_tile_partials(const DevWorld& W, hipStream_t s, double* d_out, int reset);
-void launch_tile_after_interpret(const DevWorld& W, hipStream_t s);
-void launch_tile_place(const DevWorld& W, hipStream_t s, int round, int phase, uint32_t key, int sub, int nsub);
-void launch_tile_finish(const DevWorld& W, hipStream_t s, uint32_t key, int sub, int nsub);

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_gt_scatter(const uint64_t* __res
 }
 
 // ---- segments -----------------------------------------------------------------
-struct GtCells {            // the per-cell values of k_census (world.hip)
+struct GtCells {            // the per-cell values of k_census (state.hip)
   const double* merit;
   const double* fitness;
   const int32_t* gest_time;

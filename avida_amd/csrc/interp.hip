@@ -94,7 +94,7 @@ __device__ __forceinline__ bool consume_resource(const DevWorld& W, const double
     if (spatial) *cellp = __dsub_rn(level, consumed);
     else atomicAdd(W.res_cons + slot, (unsigned long long)__dmul_rn(consumed, RES_FIX));
     // the cell's consumption this step (a newborn that replaces the organism
-    // gives back its share after the birth: world.hip newborn_credit)
+    // gives back its share after the birth: activate.hip newborn_credit)
     if (wcons) { double* cp = W.cons + (int64_t)slot * N + cell; *cp = __dadd_rn(*cp, consumed); }
   }
   const double bon = __dmul_rn(consumed, rr[RR_VALUE]);
@@ -1432,7 +1432,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
             // The parent's phenotype (merit, fitness, gestation time, copied /
             // executed size, last task counts) and the offspring's fitness and
             // RNG key: a world slice at the default knobs leaves them to
-            // finalize_key / finalize_phenotype (world.hip, placement round 0: SIMT over the
+            // finalize_key / finalize_phenotype (place.hip, placement round 0: SIMT over the
             // records, where here one lane at a time ran them with the wave
             // waiting); otherwise, or without a record, they are stored here.
             const bool defer = DEF && mode == AVGPU_MODE_WORLD && !serial;
@@ -1814,7 +1814,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
                     W.b_pcnt[(int64_t)k * rcap + rec] = pcnt[k];
                   }
                 // the inherited phenotype: one 128-B row, 16-B stores (device.h BI_*)
-                // (deferred: fitness and key left to world.hip's finalize_*, BI_FINAL bit 0)
+                // (deferred: fitness and key left to place.hip's finalize_*, BI_FINAL bit 0)
                 int32_t* irow = b_inh + (int64_t)rec * BI_WORDS;
                 const long long mb = __double_as_longlong(merit);
                 const long long fb = defer ? 0ll : __double_as_longlong(__ddiv_rn(__dmul_rn(base, bon), (double)gt));
@@ -1872,7 +1872,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
             }
           } else if (mode == AVGPU_MODE_WORLD && rec >= 0) {
             // the unmutated child, 4 sites per lane; its divide mutations are
-            // applied by k_place_pick_mut / k_tile_prep (world.hip) before placement, from
+            // applied by k_place_pick_mut / k_tile_prep (place.hip) before placement, from
             // the edits stored with the record -- keeping the per-site edit
             // composition out of this kernel's registers
             uint8_t* g = W.b_genome + (int64_t)rec * TAPE_SLOT;
@@ -2027,7 +2027,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     W.budget[cell] = spill ? (budget | (prim ? BUDGET_PRIM : 0)) : 0;
     if (spill && mode == AVGPU_MODE_WORLD) W.sdone[cell] = sdone + executed;
     // the slice's instructions (a newborn replacing this organism gives the
-    // step back the share after its birth: world.hip newborn_setup)
+    // step back the share after its birth: activate.hip newborn_setup)
     if (!NB && !spill && mode == AVGPU_MODE_WORLD && !serial) W.ran[cell] = sdone + executed;
     // merit, fitness, gestation time, copied / executed sizes and last-task
     // counts were stored at the divide (st_async)

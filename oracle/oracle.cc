@@ -1751,7 +1751,7 @@ static uint64_t genome_key(const World& w, const std::vector<uint8_t>& g) {
 }
 
 // Per-cell state digest, restating the device's k_state_digest (avida_amd/
-// csrc/world.hip): chained mix over the words of the dump_state tuple, then the
+// csrc/state.hip): chained mix over the words of the dump_state tuple, then the
 // tape in canonical bytes (handler | copied << 6 | executed << 7).  0 for a
 // cell that never held an organism.
 int orc_state_digests(void* h, int64_t first, int64_t count, uint64_t* out) {
@@ -2204,7 +2204,7 @@ static void allot_interpret(World& w, const std::vector<int64_t>& blk, double to
 // its own share of the step's remaining picks, Binomial(round(UD_s (1 - t)),
 // weight / total) from a stateless node draw of its global cell, stopping
 // before an h-divide (its offspring would need a placement this step has
-// already done).  The device's k_activate / newborn pass (world.hip,
+// already done).  The device's k_activate / newborn pass (activate.hip,
 // interp.hip NB) run the same.
 enum : uint32_t { SALT_NEWBORN = 0x4E3B0A17u };
 static int64_t newborn_budget(const World& w, int64_t cell, uint32_t t, int64_t uds, double total) {

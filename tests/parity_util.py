@@ -123,7 +123,7 @@ def _mix(z):
 
 
 def digest_of(state, ops, flags, handlers):
-    """Python restatement of the per-cell state digest (avida_amd/csrc/world.hip
+    """Python restatement of the per-cell state digest (avida_amd/csrc/state.hip
     k_state_digest, oracle orc_state_digests) from one avgpu_get_states record
     and its memory (op codes, flags bit0 copied / bit2 executed)."""
     import ctypes as C

@@ -3,7 +3,7 @@ main/cPopulation.cc:5297-5310): an offspring goes to a cell drawn from the
 whole world -- with PREFER_EMPTY, FindRandEmptyCell (:5650-5668), uniform
 among the empty cells, or any cell once the world is full; without it,
 GetUInt(size), redrawn while it is the parent and ALLOW_PARENT is 0
-(oracle soup_target, world.hip place_pick_one).  In the batch step the empty
+(oracle soup_target, place.hip place_pick_one).  In the batch step the empty
 cells are those empty at the step's end that the placement round has not
 taken.
 
