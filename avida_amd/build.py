@@ -12,7 +12,10 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["interp.hip",
+SOURCES = [# the interpreter's kernels (csrc/interp_launch.h), by far the longest compiles: started first
+           "interp_c0_rec.hip", "interp_c0.hip", "interp_lists_rec.hip", "interp_lists.hip", "serial.hip",
+           # the host side of their launches
+           "interp.hip",
            # the kernels around k_interpret, one file per subsystem (csrc/births.h is what they share)
            "state.hip", "sched.hip", "place.hip", "activate.hip", "stats.hip",
            "resources.hip", "genotypes.hip", "arbiter.hip", "lineage.hip", "landscape.hip",

@@ -1,5 +1,5 @@
 // births.h -- offspring helpers shared by placement (place.hip), activation
-// (activate.hip) and the serial world (interp.hip): the neighbourhood, the
+// (activate.hip) and the serial world (serial.hip): the neighbourhood, the
 // divide-mutation edits, ActivateOrganism / SetupOffspring of a record into a
 // cell, and a birth record's placement row, states and claim keys.
 // Paths are relative to avida-core/source/ of the reference.
@@ -77,7 +77,7 @@ __device__ __forceinline__ uint32_t neighbours_mask(const DevWorld& W, int cell,
 
 // Divide_DoMutations' edits (cpu/cHardwareBase.cc:296-569), drawn in the
 // interpreter in the reference's order and stored with the birth record
-// (interp.hip): one wave per queued offspring that has any rewrites its
+// (interp_core.h): one wave per queued offspring that has any rewrites its
 // genome -- site j of the mutated child is traced back through the edits
 // (last first, the variable-count segments in b_subs included) to a site of
 // the unmutated child or to a value an edit wrote.

@@ -8,8 +8,8 @@
 // birth queue, scratch) on one HIP device and one HIP stream.  Each entry
 // point names the reference interface it replaces in the header.  There is no
 // CPU execution path in this library: every state transition of the hot path
-// runs in the kernels of interp.hip and of state.hip, sched.hip, place.hip,
-// activate.hip and stats.hip around it.
+// runs in the interpreter's kernels (interp_launch.h, serial.hip) and in those
+// of state.hip, sched.hip, place.hip, activate.hip and stats.hip around them.
 #include "host.h"
 
 using namespace avh;
@@ -168,13 +168,13 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   W.rec = nullptr; W.rec_n = 0; W.rec_off = nullptr;
   W.seed_lo = (uint32_t)c.seed;
   W.seed_hi = (uint32_t)(c.seed >> 32);
-  // interpreter slow-op batching (interp.hip); AVGPU_SLOW_BATCH overrides (tuning)
+  // interpreter slow-op batching (interp_core.h); AVGPU_SLOW_BATCH overrides (tuning)
   W.slow_batch = env_int("AVGPU_SLOW_BATCH", 12, 1, 64);
   // the newborn pass's own: 1 -- its duration is its longest newborn's, and a
   // parked lane waiting for a batch lengthens exactly that path (1.344 ->
   // 1.323 ms per update, profiles/r06g_ab_nbsb.txt)
   W.nb_slow_batch = env_int("AVGPU_NB_SLOW_BATCH", 1, 1, 64);
-  // the kernels that queue their IO task checks (interp.hip IOQ): IO, ~45 % of
+  // the kernels that queue their IO task checks (interp_core.h IOQ): IO, ~45 % of
   // the bench population's parks, parks only on a full queue there, so the
   // same wait fills half a batch (12 against 6 against 8 against 4:
   // profiles/ioq_ab.txt)
@@ -669,7 +669,7 @@ int avgpu_load_env(avgpu_world* w, int nreact, const avgpu_reaction* r) {
     W.div_req = (W.req_task >= 0 || (!W.single_react && W.req_react >= 0) || W.single_react ||
                  W.max_task_cnt > 0) ? 1 : 0;
   }
-  // simple-environment fast path of the IO task check (interp.hip)
+  // simple-environment fast path of the IO task check (interp_core.h)
   double ttab[32];
   for (int t = 0; t < 16; t++) { ttab[t] = 1.0; ttab[16 + t] = 0.0; }
   bool simple = true;

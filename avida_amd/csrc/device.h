@@ -166,7 +166,7 @@ struct DevWorld {
   int32_t* b_count;   // [BQ_WORDS] (BQ_* below)
   int32_t* b_list;    // [n] primary record ids, appended per wave after the loop
   int32_t* b_len0;    // [rcap]  the child's length before the divide mutations (b_genome holds that child)
-  int32_t* b_edit;    // [5][rcap] its divide-mutation edits (interp.hip edit_word; 0 = none)
+  int32_t* b_edit;    // [5][rcap] its divide-mutation edits (interp_core.h edit_word; 0 = none)
   // variable-count divide-mutation edits of record r (only read when
   // seg_any): segment k holds b_pcnt[k][r] edit words from
   // b_subs[b_pofs[k][r]], applied at its place in Divide_DoMutations' order
@@ -218,7 +218,7 @@ struct DevWorld {
   uint8_t* rand_lut;  // [256] draw -> canonical code when rand_total <= 256
   int32_t slow_batch;   // parked lanes that trigger the interpreter's slow phase (1..64)
   int32_t nb_slow_batch;  // the same in the newborn pass
-  int32_t ioq_slow_batch; // the same in the main pass of the kernels that queue their IO task checks (interp.hip IOQ)
+  int32_t ioq_slow_batch; // the same in the main pass of the kernels that queue their IO task checks (interp_core.h IOQ)
   int n_react;
   // reactions, RT_STRIDE words each: task, process type, requisite min / max
   // count, has-requisite, in-use, bonus multiplier (f64), bonus addend (f64)
@@ -936,12 +936,14 @@ static inline int env_int(const char* name, int dflt, int lo, int hi) {
 // the blocks of b threads that cover n items
 static inline unsigned nblk(int64_t n, int b) { return (unsigned)((n + b - 1) / b); }
 
-// ---- interp.hip ----
+// ---- serial.hip: one update of the serial world ----
+// dW: device copy of W (avgpu_world::push_world)
+void launch_serial_update(const DevWorld& W, const DevWorld* dW, hipStream_t s);
+
+// ---- interp.hip: the interpreter's launches (its kernels: interp_launch.h) ----
 // class 0 runs densely over cells [first, first+count); classes 1..3 over their lists
 // after_class[k] (optional): event recorded after the class-k launch
-// dW: device copy of W (avgpu_world::push_world)
 // sorted: a world update's main pass (class 0 follows k_window_order's windows)
-void launch_serial_update(const DevWorld& W, const DevWorld* dW, hipStream_t s);
 void launch_interpret_classes(const DevWorld& W, const DevWorld* dW, int mode, hipStream_t s,
                               int64_t first, int64_t count, int* launches,
                               hipEvent_t* after_class = nullptr, bool sorted = false);

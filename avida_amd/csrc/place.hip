@@ -66,7 +66,7 @@ __device__ __forceinline__ unsigned long long tile_merged(const DevWorld& W, int
   return v;
 }
 
-// The rest of a deferred divide (interp.hip, BI_FINAL), in two halves that
+// The rest of a deferred divide (interp_core.h, BI_FINAL), in two halves that
 // run side by side in placement round 0's launch.  The offspring's RNG key
 // (derived from the parent's key and divide count) is the pick's, which draws
 // from it (finalize_key); the offspring's fitness (cPhenotype::DivideReset,

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(1024) void k_block_counts(DevWorld W, const double*
   }
   __syncthreads();
   if (mode == BC_TOTALS_ONLY) return;
-  for (int i = tid; i < NSHARD * PACC_STRIDE; i += 1024) W.pacc[i] = 0;   // this step's predictor (interp.hip pred_term)
+  for (int i = tid; i < NSHARD * PACC_STRIDE; i += 1024) W.pacc[i] = 0;   // this step's predictor (interp_core.h pred_term)
   // top down, only the nodes over this world's blocks [b0, b0 + nloc) (a
   // node's count depends on its ancestors' alone): a strip of T splits its
   // own subtree and the path to it, not the whole gathered world's tree

@@ -2120,7 +2120,7 @@ static int64_t densest(const int64_t* bins) {
 // (main/cPopulation.cc:610-615 AdjustSchedule at every divide).  In units of
 // the mean weight, 2^-20 fixed point (an order-free sum).  Organisms that
 // divided in this slice are left out (their next divide is a gestation away).
-// The device's pred_term (interp.hip) is the same arithmetic.
+// The device's pred_term (interp_core.h) is the same arithmetic.
 static int64_t pred_term(const World& w, const Org& o, double total, int64_t nalive, int64_t* bins) {
   const double wbar = total / (double)nalive;
   const double wi = o.merit;

@@ -158,28 +158,29 @@ def compare_digests(da, db, first=0, limit=10):
 # view over state arrays, and worlds whose organisms outgrow their slots on
 # demand.
 
-# device.h:891-894 CLASS0_SIZE .. CLASS3_SIZE (class_of :895-897)
+# device.h CLASS0_SIZE .. CLASS3_SIZE (and class_of)
 CLASS_SIZES = (320, 768, 1536, 2048)
 # The capacities a slice passes through, by route and by the class k_allot gave
 # it; an organism whose memory outgrows one capacity spills into the next.
 #  "update" (run_update, main and newborn pass): the list classes run in the
-#    class-0 launch's mixed blocks, interp.hip:406 Scap = min(S * kslot, 2048)
-#    with kslot 3 / 5 / 7 (:2207) = 960 / 1600 / 2048; a class-0 spill is
-#    continued by its own wave in a 960-site slot (:2240-2245); every later
-#    spill goes to rows 5 + 6, which run in class 3's slots (:2695)
+#    class-0 launch's mixed blocks, interp_core.h interpret_chunk's Scap =
+#    min(S * kslot, 2048) with k_interpret's kslot 3 / 5 / 7 (interp_launch.h)
+#    = 960 / 1600 / 2048; a class-0 spill is continued by its own wave in a
+#    960-site slot (k_interpret's run_chunk); every later spill goes to rows
+#    5 + 6, which run in class 3's slots (interp.hip launch_classes)
 #  "step_world" (avgpu_step, MODE_WORLD): class 0 continues in-wave as above,
-#    the list classes run their rows, Scap = S (:406, :2683-2685)
+#    the list classes run their rows, Scap = S (launch_classes' rows 1..3)
 #  "step_frozen" (avgpu_step, other modes): class 0's spills run row 4 in
-#    class 1's slots (:2688)
+#    class 1's slots (launch_classes' row 4)
 SLOT_CHAINS = {
     "update": ((320, 960, 2048), (960, 2048), (1600, 2048), (2048,)),
     "step_world": ((320, 960, 2048), (768, 2048), (1536, 2048), (2048,)),
     "step_frozen": ((320, 768, 2048), (768, 2048), (1536, 2048), (2048,)),
 }
 # organisms per chunk and blocks of the mixed launch's list classes 1 / 2 / 3
-# (interp.hip:2183-2185 MIX_B1 / MIX_B2 / MIX_B3, :2208 per = 64 / kslot)
+# (interp_launch.h MIX_B1 / MIX_B2 / MIX_B3, k_interpret's per = 64 / kslot)
 MIX_GRIDS = ((21, 512), (12, 16), (9, 8))
-PER3 = 21                      # interp.hip:2240: continued spills per group
+PER3 = 21                      # k_interpret's PER3: continued spills per group
 
 
 def state_array(backend, n=None):

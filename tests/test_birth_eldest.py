@@ -4,7 +4,7 @@ schedule): an offspring takes the cell of the reaper queue's rear entry
 (PopRear; without ALLOW_PARENT the parent's is pushed back to the rear and
 the next one taken), and ActivateOrganism pushes every newborn's cell at the
 front (:1358-1361); deaths leave the queue alone (oracle serial_eldest,
-interp.hip k_serial_update).  The queue starts as the reference's Setup
+serial.hip k_serial_update).  The queue starts as the reference's Setup
 order (cells 0..N-1, :343-347) followed by the living cells in ascending
 order (their injections).  The batch world and strips refuse the method.
 

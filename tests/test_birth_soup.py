@@ -13,7 +13,7 @@ often as 8 of the 80 empty cells predict, never in the parent's cell.  World:
 a 32x32 grid grown from 12 mutants until it is full, GPU == oracle bit for
 bit under every PREFER_EMPTY / ALLOW_PARENT combination.  The serial world
 (the reference's schedule) places soup births with FindRandEmptyCell on the
-reference's persistent empty-cell array (oracle serial_soup, interp.hip
+reference's persistent empty-cell array (oracle serial_soup, serial.hip
 k_serial_update): GPU == oracle, and the batch world's growth is compared
 with it over many seeds (two-sample tests)."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""The interpreter's queued IO task checks (interp.hip, IOQ): in the simple
+"""The interpreter's queued IO task checks (interp_core.h, IOQ): in the simple
 environment without finite resources an IO does at once only what the organism
 sees and queues its task check, up to QUEUE_DEPTH per lane; the wave evaluates
 the queues together when a lane's is full, before a divide of a lane that has
@@ -17,7 +17,7 @@ import oracle_lib as ol
 import parity_util as pu
 
 CAP = capi.MAX_GENOME
-QUEUE_DEPTH = 3            # interp.hip: IOQ_FULL
+QUEUE_DEPTH = 3            # interp_core.h: IOQ_FULL
 STAT_FIELDS = ("num_organisms", "insts_executed", "births", "deaths", "divides", "births_dropped",
                "births_overwritten", "births_cancelled", "cum_insts_executed", "cum_births", "slices")
 

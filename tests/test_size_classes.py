@@ -1,7 +1,7 @@
 """Directed parity tests for the interpreter's LDS size classes and spills
-(avida_amd/csrc/interp.hip: k_interpret, interpret_chunk; device.h need_of /
-class_of).  The oracle has no size classes, so every world here is built to
-outgrow its slots on demand (parity_util: construction 1 a handed-in organism
+(avida_amd/csrc/interp_launch.h k_interpret, interp_core.h interpret_chunk;
+device.h need_of / class_of).  The oracle has no size classes, so every world
+here is built to outgrow its slots on demand (parity_util: construction 1 a handed-in organism
 about to divide and then allocate, construction 2 a chain of h-allocs at
 REQUIRE_ALLOCATE 0, construction 3 copy insertions from constant recorded
 streams), and the spills a call must make are read off the oracle's own states
@@ -71,7 +71,7 @@ class Scenario:
         elif env == "generic":
             # IP_GENERIC: a twice-only requisite is outside the simple form (capi.hip avgpu_load_env's `simple` loop:
             # of the requisites only max_count 1, the once mask, and INT32_MAX keep `simple`;
-            # interp.hip:2614-2619 interp_of then chooses the generic kernel)
+            # interp.hip interp_of then chooses the generic kernel)
             for r in self.env:
                 r.has_requisite, r.min_count, r.max_count = 1, 0, 2
         self.n = side * side

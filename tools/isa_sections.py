@@ -1,10 +1,11 @@
 """Static instruction mix per marked section of one interpreter kernel.
 
 Build the marked assembly first (markers are `asm volatile` comments at the
-phase-clock points of interp.hip, compiled only with -DAVGPU_ISA_MARKS):
+phase-clock points of interp_core.h, compiled only with -DAVGPU_ISA_MARKS;
+interp_c0.hip holds class 0's kernels, interp_lists.hip the list classes'):
 
   hipcc -O3 --offload-arch=gfx950 -std=c++17 -ffp-contract=off \
-      -DAVGPU_ISA_MARKS --offload-device-only -S -o marks.s avida_amd/csrc/interp.hip
+      -DAVGPU_ISA_MARKS --offload-device-only -S -o marks.s avida_amd/csrc/interp_c0.hip
   python tools/isa_sections.py marks.s [320] [0] [Lb1ELb1ELb1]
 
 Counts are static (instructions between a marker and the next one in layout
