@@ -168,17 +168,22 @@ int setup_world(avgpu_world* w, int64_t n, bool test_buffers) {
   W.rec = nullptr; W.rec_n = 0; W.rec_off = nullptr;
   W.seed_lo = (uint32_t)c.seed;
   W.seed_hi = (uint32_t)(c.seed >> 32);
-  // interpreter slow-op batching (interp_core.h); AVGPU_SLOW_BATCH overrides (tuning)
-  W.slow_batch = env_int("AVGPU_SLOW_BATCH", 12, 1, 64);
+  // interpreter slow-op batching (interp_core.h); AVGPU_SLOW_BATCH overrides
+  // (tuning).  Class 0 runs pop and push without parking (its register stacks
+  // are in depth order), so with three quarters of the parks gone the same wait
+  // fills a smaller batch: 6 against 8 against 12 in the resource environment,
+  // whose IO still parks (profiles/stack_shift_ab.txt)
+  W.slow_batch = env_int("AVGPU_SLOW_BATCH", 6, 1, 64);
   // the newborn pass's own: 1 -- its duration is its longest newborn's, and a
   // parked lane waiting for a batch lengthens exactly that path (1.344 ->
   // 1.323 ms per update, profiles/r06g_ab_nbsb.txt)
   W.nb_slow_batch = env_int("AVGPU_NB_SLOW_BATCH", 1, 1, 64);
-  // the kernels that queue their IO task checks (interp_core.h IOQ): IO, ~45 % of
-  // the bench population's parks, parks only on a full queue there, so the
-  // same wait fills half a batch (12 against 6 against 8 against 4:
-  // profiles/ioq_ab.txt)
-  W.ioq_slow_batch = env_int("AVGPU_IOQ_SLOW_BATCH", 6, 1, 64);
+  // the kernels that queue their IO task checks (interp_core.h IOQ): there IO
+  // parks only on a full queue and (class 0) pop and push not at all -- what
+  // still parks is h-alloc, h-search, h-divide and long labels, a few percent
+  // of the instructions, and a lane waiting for company costs more than a slow
+  // phase for one lane (1 against 2 / 3 / 4 / 6 / 8: profiles/stack_shift_ab.txt)
+  W.ioq_slow_batch = env_int("AVGPU_IOQ_SLOW_BATCH", 1, 1, 64);
   W.row0 = 0;
   W.global_rows = c.world_y;
   W.rows = c.world_y;

@@ -26,6 +26,7 @@
 #pragma once
 #include "device.h"
 #include "births.h"
+#include "stack_rot.h"
 
 #pragma clang fp contract(off)
 
@@ -424,7 +425,10 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
   const int QUADS = MIX ? QUADS0 * kslot : QUADS0;
   const int Scap = MIX ? min(S * kslot, AVGPU_MAX_GENOME) : S;
   // class 0 keeps the two stacks in VGPRs (sv[]): without their 5 KiB of LDS a
-  // block needs 26 KiB and 6 blocks fit a CU instead of 5
+  // block needs 26 KiB and 6 blocks fit a CU instead of 5.  It holds them in
+  // depth order (stack_rot.h: sv[10 k + d] = the entry at depth d of stack k),
+  // rotated from the record's rings after the staging and back before the
+  // write-back, so that a pop or push is 10 moves and runs without parking
   constexpr bool VSTK = (S == CLASS0_SIZE);
   constexpr int STK_WORDS = VSTK ? 0 : STK_LDS_WORDS;
   // one __shared__ object: tapes | stacks | the tables (TAB_*)
@@ -655,6 +659,13 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     for (int q = 0; q < AVGPU_NUM_LOGIC_TASKS; q++) nzm |= (tc[q] > 0 ? 1u : 0u) << q;
     dnd = W.num_div[cell];
   }
+  // the record's rings -> depth order (a stack whose pointer is 0 in every
+  // lane has nothing to rotate: fresh organisms, newborn waves, and stack 1
+  // wherever no organism has used swap-stk)
+  if (VSTK) {
+    if (__ballot(CTL_SP0(ctl) != 0u) != 0ull) stack_ring_to_depth<0, AVGPU_STACK_SIZE>(sv, CTL_SP0(ctl));
+    if (__ballot(CTL_SP1(ctl) != 0u) != 0ull) stack_ring_to_depth<1, AVGPU_STACK_SIZE>(sv, CTL_SP1(ctl));
+  }
   prim0 = prim;
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0), visible to the compiler's waitcnt tracking
   __syncthreads();
@@ -727,6 +738,36 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
 #define SETREG(i, v) do { const int _v = (v); if ((i) == 0) r0 = _v; else if ((i) == 1) r1 = _v; else r2 = _v; } while (0)
 #define GETHEAD(i) ((i) == 0 ? ip : ((i) == 1 ? rh : ((i) == 2 ? wh : fh)))
 #define SETHEAD(i, v) do { const int _v = (v); if ((i) == 0) ip = _v; else if ((i) == 1) rh = _v; else if ((i) == 2) wh = _v; else fh = _v; } while (0)
+
+  // pop / push on the register stacks (:2698 / :2705, cCPUStack::Pop / Push)
+  // in depth order.  The pointer in ctl moves as the ring's does (a push is
+  // +9 mod 10).  The entries move by selects in place, no index compare: the
+  // pushing lanes' one deeper, from the bottom up, then the popping lanes' one
+  // shallower, from the top down -- a lane is in one of the two passes, and
+  // written this way no entry needs a copy.  Stack 1 is rare (swap-stk): its
+  // passes run only for the lanes on it.  (Macros: with sv[] captured by a
+  // lambda the stacks went to scratch.)
+#define STK_PASS(K, q, p, in) do {                                                                 \
+    _Pragma("unroll") for (int d = AVGPU_STACK_SIZE - 1; d > 0; d--)                               \
+      sv[K * AVGPU_STACK_SIZE + d] = (q) ? sv[K * AVGPU_STACK_SIZE + d - 1] : sv[K * AVGPU_STACK_SIZE + d]; \
+    sv[K * AVGPU_STACK_SIZE] = (q) ? (in) : sv[K * AVGPU_STACK_SIZE];                              \
+    _Pragma("unroll") for (int d = 0; d < AVGPU_STACK_SIZE - 1; d++)                               \
+      sv[K * AVGPU_STACK_SIZE + d] = (p) ? sv[K * AVGPU_STACK_SIZE + d + 1] : sv[K * AVGPU_STACK_SIZE + d]; \
+    sv[(K + 1) * AVGPU_STACK_SIZE - 1] = (p) ? 0 : sv[(K + 1) * AVGPU_STACK_SIZE - 1];             \
+  } while (0)
+#define VSTK_OP(push, r) do {                                                                      \
+    const bool _q = (push);                                                                        \
+    const bool _s1 = (ctl & CTL_CURSTK) != 0u;                                                     \
+    const uint32_t _sh = _s1 ? 4u : 0u;                                                            \
+    uint32_t _sp = ((ctl >> _sh) & 0xFu) + (_q ? (uint32_t)AVGPU_STACK_SIZE - 1u : 1u);            \
+    _sp = _sp >= (uint32_t)AVGPU_STACK_SIZE ? _sp - (uint32_t)AVGPU_STACK_SIZE : _sp;              \
+    ctl = (ctl & ~(0xFu << _sh)) | (_sp << _sh);                                                   \
+    const int _in = GETREG(r);                                                                     \
+    const int _top = _s1 ? sv[AVGPU_STACK_SIZE] : sv[0];                                           \
+    STK_PASS(0, _q && !_s1, !_q && !_s1, _in);                                                     \
+    if (_s1) STK_PASS(1, _q, !_q, _in);                                                            \
+    if (!_q) SETREG(r, _top);                                                                      \
+  } while (0)
 
   // Requests for the O(memory) parts of heavy instructions -- the divide's
   // flag counts, offspring copy and flag clearing, h-alloc's fill, h-search's
@@ -849,6 +890,15 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     CK(0);
     if (FAST_OPS & obit) adv = fast_op(op, r, r0, r1, r2, ip, rh, wh, fh, ctl, M);
     CK(1);
+    // pop / push on the register stacks: no park
+    bool inl_done = false;
+    if (VSTK && (op == AVGPU_H_POP || op == AVGPU_H_PUSH)) {
+      inl_done = true;
+      VSTK_OP(op == AVGPU_H_PUSH, r);
+    }
+    // (the clock of the block above counts as the slow switch's pop case did;
+    // in the marked assembly it is section CK1, h-copy and what follows CKC0)
+    if (VSTK) CKC(0);
     if (op == AVGPU_H_H_COPY) {                               // :7130 Inst_HeadCopy
       rh = rha;
       wh = wha;
@@ -997,7 +1047,6 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     // inside the window (the copy loop's short labels): no park, no label
     // read.  The window holds sites ipa+1 .. ipa+avail; a label that may run
     // past them parks and reads its own 16-byte window in the slow phase.
-    bool inl_done = false;
     if (op == AVGPU_H_IF_LABEL && k_max_label_exe == 1) {
       const int base = ip + 1;
       const int avail = 7 - (ipa & 3);
@@ -1055,27 +1104,18 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
       switch (op) {
       case AVGPU_H_POP:                                       // :2698, cCPUStack::Pop
       case AVGPU_H_PUSH: {                                    // :2705, cCPUStack::Push
-        // one case for both, so that a wave's pops and pushes share one pass
-        // over the register stacks: Push moves the pointer down and stores,
+        // the kernels whose stacks are in LDS (VSTK: done without parking,
+        // above).  One case for both: Push moves the pointer down and stores,
         // Pop reads, clears and moves it up
+        if (VSTK) break;
         const bool push = op == AVGPU_H_PUSH;
         const int k = (ctl & CTL_CURSTK) ? 1 : 0;
         int sp = k ? CTL_SP1(ctl) : CTL_SP0(ctl);
         if (push) sp = (sp == 0) ? AVGPU_STACK_SIZE - 1 : sp - 1;
         const int nv = push ? GETREG(r) : 0;
-        int v = 0;
-        if (VSTK) {
-          const int idx = k * AVGPU_STACK_SIZE + sp;
-#pragma unroll
-          for (int i = 0; i < 2 * AVGPU_STACK_SIZE; i++) {
-            v = (i == idx) ? sv[i] : v;
-            sv[i] = (i == idx) ? nv : sv[i];
-          }
-        } else {
-          int32_t* slot = stk + (k * AVGPU_STACK_SIZE + sp) * 64 + lane;
-          v = *slot;
-          *slot = nv;
-        }
+        int32_t* slot = stk + (k * AVGPU_STACK_SIZE + sp) * 64 + lane;
+        const int v = *slot;
+        *slot = nv;
         if (!push) {
           sp = (sp + 1 == AVGPU_STACK_SIZE) ? 0 : sp + 1;
           SETREG(r, v);
@@ -1988,6 +2028,8 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
   }
 #undef CK
 #undef CKC
+#undef STK_PASS
+#undef VSTK_OP
 #undef GETREG
 #undef SETREG
 #undef GETHEAD
@@ -2000,6 +2042,11 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
   const uint64_t clk2 = __builtin_amdgcn_s_memtime();
 #endif
   __syncthreads();
+  // the register stacks back to the record's rings
+  if (VSTK) {
+    if (__ballot(CTL_SP0(ctl) != 0u) != 0ull) stack_depth_to_ring<0, AVGPU_STACK_SIZE>(sv, CTL_SP0(ctl));
+    if (__ballot(CTL_SP1(ctl) != 0u) != 0ull) stack_depth_to_ring<1, AVGPU_STACK_SIZE>(sv, CTL_SP1(ctl));
+  }
   if (active) {
     // the execution record: words 0..51 in 13 16-byte stores (whole 32-B
     // sectors of the cell's own lines)
