@@ -379,6 +379,7 @@ EXPORTED = [
     "avgpu_enable_lineage", "avgpu_get_lineage", "avgpu_set_lineage", "avgpu_prune_lineage", "avgpu_last_lineage_ms",
     "avgpu_landscapes", "avgpu_set_landscape_chunk", "avgpu_last_landscape_ms",
     "avgpu_landscapes_indel", "avgpu_landscape_pairs",
+    "avgpu_genome_distances", "avgpu_cell_distances", "avgpu_site_histogram", "avgpu_last_distance_ms",
 ]
 
 
@@ -674,6 +675,22 @@ def load_product(path=None):
     lib.avgpu_last_landscape_ms.restype = C.c_int
     lib.avgpu_last_landscape_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                             C.POINTER(C.c_int64)]
+    # genetic distances and the consensus histogram: the product only (the
+    # oracle runs avida_amd.distance's specification); a diagnostic library may
+    # be an earlier build without them
+    if p == LIB_PATH or hasattr(lib, "avgpu_genome_distances"):
+        I32P = C.POINTER(C.c_int32)
+        lib.avgpu_genome_distances.restype = C.c_int
+        lib.avgpu_genome_distances.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), I32P, C.c_int64,
+                                               I32P, I32P, I32P, I32P]
+        lib.avgpu_cell_distances.restype = C.c_int
+        lib.avgpu_cell_distances.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.c_int32,
+                                             I32P, I32P]
+        lib.avgpu_site_histogram.restype = C.c_int
+        lib.avgpu_site_histogram.argtypes = [C.c_void_p, C.c_int64, C.c_int64, I32P, C.POINTER(C.c_int64)]
+        lib.avgpu_last_distance_ms.restype = C.c_int
+        lib.avgpu_last_distance_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64)]
     if path is None:
         _lib = lib
     return lib

@@ -1197,3 +1197,24 @@ void launch_land_rows(const LandScratch& S, hipStream_t s, int distance);
 // the pair mutants' tiles [t0, t1) against S.chart, and their rows
 void launch_land_epi_reduce(const LandScratch& S, hipStream_t s, int64_t m0, int64_t t0, int64_t t1);
 void launch_land_epi_rows(const LandScratch& S, hipStream_t s);
+// genetic distances and the consensus histogram (distance.hip):
+// the world's scratch, grown by 1.25x with the largest call seen
+struct DistScratch {
+  uint8_t* gen;             // the call's genomes, each at a 16-B aligned offset, zero padded to 16 B
+                            // (avgpu_cell_distances: the reference genome in canonical codes)
+  int64_t* off;             // [n] their offsets
+  int32_t* len;             // [n]
+  int32_t* pair_a;          // [npairs] indices into the n genomes
+  int32_t* pair_b;
+  int32_t* ham;             // [npairs] or [count]
+  int32_t* edit;
+  int32_t* hist;            // [TAPE_SLOT][AVGPU_MAX_INST + 1] by handler, column 0 "no site"
+  unsigned long long* living;   // the living cells k_site_hist counted
+};
+static_assert(AVGPU_MAX_GENOME == TAPE_SLOT, "a site histogram row per tape site (MAX_GENOME_LENGTH)");
+// one wave per pair / per cell; a NULL-ed output (want_* false) is not computed
+void launch_pair_dist(const DistScratch& S, hipStream_t s, int npairs, bool want_ham, bool want_edit);
+void launch_cell_dist(const DevWorld& W, const DistScratch& S, hipStream_t s, int64_t first, int64_t count,
+                      int ref_len, bool want_ham, bool want_edit);
+// S.hist and S.living zeroed by the caller
+void launch_site_hist(const DevWorld& W, const DistScratch& S, hipStream_t s, int64_t first, int64_t count);

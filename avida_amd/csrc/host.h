@@ -275,6 +275,17 @@ struct avgpu_world {
   double land_ms = 0.0;
   int64_t land_mutants = 0, land_runs = 0;
   avgpu_world* land = nullptr;
+  // genetic distances and the consensus histogram (avgpu_genome_distances,
+  // avgpu_cell_distances, avgpu_site_histogram; distance.hip): dist views the
+  // buffers, each allocated at its first use and grown by 1.25x
+  DistScratch dist = {};
+  avh::DevBuf<uint8_t> dist_in;        // the call's inputs: genomes, offsets, lengths, pairs
+  avh::DevBuf<int32_t> dist_out;       // its results: hamming, then edit
+  avh::DevBuf<int32_t> dist_hist;      // the histogram, then the living count (8-B aligned)
+  int64_t dist_in_cap = 0, dist_out_cap = 0;
+  avh::Event ev_dist[2];
+  double dist_ms = 0.0;
+  int64_t dist_pairs = 0, dist_cells = 0;
 
   // the one way to make an array that lives as long as the world: zero-filled
   // in stream order, freed with the world

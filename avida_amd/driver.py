@@ -12,8 +12,11 @@ Events on this path (main/cEventList.cc syntax "u <start>[:<interval>[:<end>]]")
 Inject <org> [cell] [merit], InjectAll <org> [merit], InjectSequence <seq>
 [start] [end] [merit], LoadPopulation <file> [update] [cellid_offset] (.pop /
 .spop, avida_amd/population.py), SavePopulation [name] (<name>-<update>.spop),
-Print{Count,Average,Tasks,Time,Resource,Dominant}Data [file], SaveCheckpoint
-[file] / LoadCheckpoint <file> (full hardware state, avida_amd/checkpoint.py;
+Print{Count,Average,Tasks,Time,Resource,Dominant}Data [file],
+PrintGeneticDistanceData <ref.org> [file], PrintPopulationDistanceData
+<ref.org> [file], CalcConsensus [lines_saved] (avida_amd/distance.py; the .org
+path is relative to the config directory), SaveCheckpoint [file] /
+LoadCheckpoint <file> (full hardware state, avida_amd/checkpoint.py;
 after LoadCheckpoint the driver's update counter is the checkpoint's, so the
 next update processed is the one after it and later events fire by that
 numbering, as LoadPopulation's update argument does), Exit.  Other Print* events write nothing; anything else is an error.
@@ -27,7 +30,7 @@ import ctypes as C
 import os
 import sys
 
-from . import capi, checkpoint, datafiles, files, population, systematics
+from . import capi, checkpoint, datafiles, distance, files, population, systematics
 
 
 class ProductWorld:
@@ -138,6 +141,20 @@ class ProductWorld:
         from . import landscape
         return landscape.full(self, genomes, distance, chart)
 
+    def pair_distances(self, genomes, pairs):
+        """(hamming, edit) of pairs of genomes on the device (avgpu_genome_distances)"""
+        return distance.pair_distances(self, genomes, pairs)
+
+    def cell_distances(self, ref, first=0, count=None):
+        """(hamming, edit) of every cell's organism to the genome `ref`, -1
+        for an empty cell (avgpu_cell_distances)"""
+        return distance.cell_distances(self, ref, first, count)
+
+    def site_histogram(self, first=0, count=None):
+        """(hist, num_living): CalcConsensus' per-site instruction histogram
+        of the living organisms (avgpu_site_histogram)"""
+        return distance.site_histogram(self, first, count)
+
     def resources(self, spatial=False):
         lv = (C.c_double * max(1, self.nres))()
         self._call("get_resources", self.h, lv, None)
@@ -195,7 +212,7 @@ class Driver:
         self.data_dir = data_dir
         # genotype classification runs every update when a data file needs it
         # (the reference's systematics manager classifies every birth)
-        need = {"PrintCountData", "PrintDominantData", "SavePopulation", "PrintAverageData"}
+        need = {"PrintCountData", "PrintDominantData", "SavePopulation", "PrintAverageData", *distance.Actions.NAMES}
         # (on the device where the world keeps the arbiter there, else on the host)
         kind = systematics.DeviceGenotypeArbiter if hasattr(self.world, "classify_genotypes") \
             else systematics.GenotypeArbiter
@@ -210,6 +227,8 @@ class Driver:
             self.arbiter = systematics.DeviceGenotypeArbiter(int(acfg.get("THRESHOLD", 3)), lineage=True)
             self.arbiter.enable(self.world)
         self.rec.arbiter = self.arbiter
+        # the genetic-distance actions (avida_amd/distance.py): on the device where the world answers there
+        self.dist = distance.Actions(self.world, self.iset, data_dir, config_dir)
         self.done = False
         self.update = -1
 
@@ -289,6 +308,8 @@ class Driver:
             self.update = int(stats.update)          # the next update is the one after the checkpoint's
             if isinstance(self.arbiter, systematics.DeviceGenotypeArbiter):
                 self.arbiter.attach(w)               # the checkpoint carried the arbiter's state
+        elif action in distance.Actions.NAMES:
+            self.dist.run(action, args, self.arbiter, max(self.update, 0))
         elif action == "Exit":
             self.done = True
         elif action.startswith("Print"):
@@ -311,6 +332,7 @@ class Driver:
                 if _fires(trig, start, self.update):
                     self._action(action, args)
         self.rec.close()
+        self.dist.close()
         return self.update
 
 

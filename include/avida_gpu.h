@@ -892,6 +892,56 @@ int avgpu_set_landscape_chunk(avgpu_world* w, int64_t cells);
  * pairs: the one-step and the pair mutants together). */
 int avgpu_last_landscape_ms(avgpu_world* w, double* device_ms, int64_t* mutants, int64_t* gestations);
 
+/* ---- genetic distances and the consensus genome -----------
+ * InstructionSequence::FindHammingDistance at offset 0
+ * (core/InstructionSequence.cc:488-504): the length difference plus the
+ * mismatches over the first min(len) sites; FindEditDistance (:547-613): the
+ * Levenshtein distance.  One wave per pair on the device; every result is an
+ * exact integer.  The three calls are stream-ordered behind the queued
+ * updates and complete on return; the world, its statistics and its random
+ * streams are not changed.  Their scratch belongs to the world (grown by
+ * 1.25x with the largest call, freed by avgpu_destroy).  A strip tile:
+ * AVGPU_EUNSUPPORTED.  AVGPU_EINVAL leaves every output untouched. */
+/* Distances of npairs pairs among n genomes: it replaces a host loop over
+ * FindHammingDistance / FindEditDistance.  genomes: op codes packed back to
+ * back, lens[i] each, as avgpu_landscapes takes them; pair p is (pair_a[p],
+ * pair_b[p]), indices into the n genomes.  hamming, edit: npairs results
+ * each; either may be NULL and is then not computed.  AVGPU_EINVAL: n or
+ * npairs <= 0, a length outside 1..AVGPU_MAX_GENOME, an op code outside the
+ * instruction set, a pair index outside 0..n-1, a NULL world, both outputs
+ * NULL. */
+int avgpu_genome_distances(avgpu_world* w, int n, const uint8_t* genomes, const int32_t* lens, int64_t npairs,
+                           const int32_t* pair_a, const int32_t* pair_b, int32_t* hamming, int32_t* edit);
+/* Distances of the organisms of cells first .. first+count-1 to one reference
+ * genome (ref_len op codes): the per-genotype loops of
+ * PrintGeneticDistanceData (actions/PrintActions.cc:2725-2765),
+ * PrintPopulationDistanceData (:2792-2851) and CalcConsensus (:3165-3175)
+ * without a tape crossing to the host.  An organism's genome is the first
+ * birth_length sites of its memory, as SavePopulation takes a member's genome
+ * (a site past its memory counts as op 0, as avgpu_get_states hands it out);
+ * the comparison is by handler, so two op codes of one handler are equal.
+ * hamming, edit: count results each (either may be NULL); an empty cell
+ * answers -1 in both.  AVGPU_EINVAL: a cell range outside the world or
+ * count <= 0, ref_len outside 1..AVGPU_MAX_GENOME, an op code outside the
+ * instruction set, a NULL world, both outputs NULL. */
+int avgpu_cell_distances(avgpu_world* w, int64_t first_cell, int64_t count, const uint8_t* ref, int32_t ref_len,
+                         int32_t* hamming, int32_t* edit);
+/* CalcConsensus' histograms (actions/PrintActions.cc:3088-3114) over the
+ * living organisms of a cell range: hist[j][1 + op] counts the organisms
+ * whose genome (as above) has op at site j, hist[j][0] those whose genome
+ * ends before site j (the reference's -1 bin), for j < AVGPU_MAX_GENOME =
+ * MAX_GENOME_LENGTH (include/public/avida/core/Definitions.h:29).  hist:
+ * AVGPU_MAX_GENOME x (AVGPU_MAX_INST + 1) int32; num_living (may be NULL):
+ * the organisms counted, the sum of every row.  Integer atomics only: the
+ * same bytes from every call.  AVGPU_EINVAL: a cell range outside the world
+ * or count <= 0, a NULL world or hist. */
+int avgpu_site_histogram(avgpu_world* w, int64_t first_cell, int64_t count, int32_t* hist, int64_t* num_living);
+/* Timing of the last of the three calls above (no reference equivalent): the
+ * device time of its kernels in ms (HIP events on the world's stream), the
+ * pairs it compared (avgpu_genome_distances, else 0) and the cells it read
+ * (avgpu_cell_distances and avgpu_site_histogram, else 0). */
+int avgpu_last_distance_ms(avgpu_world* w, double* device_ms, int64_t* pairs, int64_t* cells);
+
 /* ---- statistics / multi-GPU plumbing ------------------------------------ */
 /* the last update's statistics (reduced here if that update ran with out == NULL) */
 int avgpu_get_stats(avgpu_world* w, avgpu_update_stats* out);
