@@ -68,6 +68,35 @@ __device__ __forceinline__ uint32_t byte_mask(int w4, int from, int to) {
   for (int q = 0; q < 4; q++) m |= (w4 + q >= from && w4 + q < to) ? (0xFFu << (8 * q)) : 0u;
   return m;
 }
+// Sites [a, b) of the lane's own tape T (a 16-byte aligned LDS slot) set to the
+// byte f4 & 0xFF, f4 being that byte four times: stores alone -- no LDS read,
+// no other lane, no wait.  Naturally aligned stores climb from a to a quad
+// boundary (1, 2, 4, 8 bytes, each only while it ends at or before b), quads
+// cover the body, and the sizes descend again to b; a size that did not fit on
+// the way up leaves less than itself, which the way down covers.  No byte
+// outside [a, b) is written.
+__device__ __forceinline__ void tape_fill(uint8_t* T, int a, int b, uint32_t f4) {
+  typedef __attribute__((address_space(3))) uint8_t l8_t;
+  typedef __attribute__((address_space(3))) uint16_t l16_t;
+  typedef __attribute__((address_space(3))) uint32_t l32_t;
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  typedef __attribute__((address_space(3))) u32x2 l64_t;
+  typedef __attribute__((address_space(3))) u32x4 l128_t;
+  const u32x2 f8 = {f4, f4};
+  const u32x4 f16 = {f4, f4, f4, f4};
+  l8_t* t = (l8_t*)T;
+  int p = a;
+  if ((p & 1) && p + 1 <= b) { t[p] = (uint8_t)f4; p += 1; }
+  if ((p & 2) && p + 2 <= b) { *(l16_t*)(t + p) = (uint16_t)f4; p += 2; }
+  if ((p & 4) && p + 4 <= b) { *(l32_t*)(t + p) = f4; p += 4; }
+  if ((p & 8) && p + 8 <= b) { *(l64_t*)(t + p) = f8; p += 8; }
+  for (; p + 16 <= b; p += 16) *(l128_t*)(t + p) = f16;
+  if (p + 8 <= b) { *(l64_t*)(t + p) = f8; p += 8; }
+  if (p + 4 <= b) { *(l32_t*)(t + p) = f4; p += 4; }
+  if (p + 2 <= b) { *(l16_t*)(t + p) = (uint16_t)f4; p += 2; }
+  if (p + 1 <= b) t[p] = (uint8_t)f4;
+}
 __device__ __forceinline__ int wave_sum_i32(int v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   return v;
@@ -772,9 +801,11 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
   // Requests for the O(memory) parts of heavy instructions -- the divide's
   // flag counts, offspring copy and flag clearing, h-alloc's fill, h-search's
   // label scan.  A lane decodes such an instruction and posts a request; the
-  // whole wave then serves the requests one lane at a time, 64 sites per
-  // instruction (DESIGN.md "Cooperative heavy ops").  Run per lane, every
-  // iteration of the wave paid for the longest such loop of any of its lanes.
+  // whole wave then serves the divides and searches one lane at a time, 64
+  // sites per instruction (DESIGN.md "Cooperative heavy ops").  Run per lane,
+  // every iteration of the wave paid for the longest such loop of any of its
+  // lanes.  The fill is the exception: it reads nothing, so every requester
+  // writes its own tape at once, a quad per store (tape_fill).
   const int RQ_NONE = 0, RQ_DIVIDE = 1, RQ_FILL = 2, RQ_SEARCH = 3;
   const uint32_t fill4 = (uint32_t)W.fill_code * 0x01010101u;
   // Slow ops (stack, IO, h-alloc, h-divide, h-search, if-label) are batched:
@@ -1346,8 +1377,12 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
     // a divide reads the bonus and resets the counts: apply its queued rewards first
     if (k_env_res_mask != 0u && __ballot(rpq != 0u && (rq == RQ_DIVIDE || (rpq >> 30) == 3u)) != 0ull)
       res_flush<GTAB>(W, N, cell, rpq, bonus, rc, ttab, tmul, tadd, k_env_res_mask, mode == AVGPU_MODE_WORLD);
-    // ---- wave phase: serve the posted requests, one lane at a time ----
-    unsigned long long pend = __ballot(rq != RQ_NONE);
+    // ---- h-alloc's fill: Allocate_Main's new sites [qa, qb) get op 0
+    // (ALLOC_METHOD 0/1), every requester its own tape, all at once ----
+    static_assert(STRIDE0 % 16 == 0, "tape slots start on a quad (tape_fill)");
+    if (rq == RQ_FILL) tape_fill(T, qa, qb, fill4);
+    // ---- wave phase: serve the divides and searches, one lane at a time ----
+    unsigned long long pend = __ballot(rq == RQ_DIVIDE || rq == RQ_SEARCH);
     while (pend) {
       const int L = __ffsll((long long)pend) - 1;            // wave-uniform
       pend &= pend - 1ull;
@@ -1355,13 +1390,7 @@ __device__ __forceinline__ int interpret_chunk(const DevWorld* __restrict__ Wp, 
       const int a = __shfl(qa, L), b = __shfl(qb, L);
       uint32_t* TL32 = lds32 + L * (STRIDE / 4);
       const uint8_t* TL = lds + L * STRIDE;
-      if (kind == RQ_FILL) {
-        // Allocate_Main: new sites [a, b) get op 0 (ALLOC_METHOD 0/1)
-        for (int w = (a >> 2) + lane; (w << 2) < b; w += 64) {
-          const uint32_t keep = byte_mask(w << 2, a, b);
-          TL32[w] = (TL32[w] & ~keep) | (fill4 & keep);
-        }
-      } else if (kind == RQ_SEARCH) {
+      if (kind == RQ_SEARCH) {
         // FindLabel(0) -> FindLabel_Forward(label, memory, 0) (:1177-1295).
         // The reference probes every label_size sites and, inside a probed
         // nop run, tests every offset; every maximal nop run that can hold the
