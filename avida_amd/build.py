@@ -19,9 +19,10 @@ SOURCES = [# the interpreter's kernels (csrc/interp_launch.h), by far the longes
            # the kernels around k_interpret, one file per subsystem (csrc/births.h is what they share)
            "state.hip", "sched.hip", "place.hip", "activate.hip", "stats.hip",
            "resources.hip", "genotypes.hip", "arbiter.hip", "lineage.hip", "landscape.hip", "distance.hip",
+           "popevents.hip",
            # the host side of the C ABI, one file per subsystem (csrc/host.h is what they share)
            "capi.hip", "capi_serial.hip", "capi_systematics.hip", "capi_state.hip", "capi_landscape.hip",
-           "capi_distance.hip", "capi_resources.hip", "capi_tiles.hip"]
+           "capi_distance.hip", "capi_popevents.hip", "capi_resources.hip", "capi_tiles.hip"]
 OUT = os.path.join(HERE, "libavida_gpu.so")
 # diagnostic variant with per-phase s_memtime clocks (tools/phase_clocks.py only)
 OUT_CLK = os.path.join(HERE, "libavida_gpu_clk.so")

@@ -380,6 +380,8 @@ EXPORTED = [
     "avgpu_landscapes", "avgpu_set_landscape_chunk", "avgpu_last_landscape_ms",
     "avgpu_landscapes_indel", "avgpu_landscape_pairs",
     "avgpu_genome_distances", "avgpu_cell_distances", "avgpu_site_histogram", "avgpu_last_distance_ms",
+    "avgpu_kill_cells", "avgpu_kill_prob", "avgpu_kill_rect", "avgpu_kill_genotypes", "avgpu_keep_sample",
+    "avgpu_last_event_ms",
 ]
 
 
@@ -691,6 +693,22 @@ def load_product(path=None):
         lib.avgpu_last_distance_ms.restype = C.c_int
         lib.avgpu_last_distance_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
                                                C.POINTER(C.c_int64)]
+    # population events (avida_amd/popevents.py): the product only; a diagnostic
+    # library may be an earlier build without them
+    if p == LIB_PATH or hasattr(lib, "avgpu_kill_cells"):
+        V, I64, U64, I64P = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_int64)
+        lib.avgpu_kill_cells.restype = C.c_int
+        lib.avgpu_kill_cells.argtypes = [V, V, I64, I64P]
+        lib.avgpu_kill_prob.restype = C.c_int
+        lib.avgpu_kill_prob.argtypes = [V, C.c_double, U64, I64P]
+        lib.avgpu_kill_rect.restype = C.c_int
+        lib.avgpu_kill_rect.argtypes = [V, C.c_int, C.c_int, C.c_int, C.c_int, I64P]
+        lib.avgpu_kill_genotypes.restype = C.c_int
+        lib.avgpu_kill_genotypes.argtypes = [V, V, I64, C.c_double, U64, I64P]
+        lib.avgpu_keep_sample.restype = C.c_int
+        lib.avgpu_keep_sample.argtypes = [V, I64, U64, I64P]
+        lib.avgpu_last_event_ms.restype = C.c_int
+        lib.avgpu_last_event_ms.argtypes = [V, C.POINTER(C.c_double), I64P]
     if path is None:
         _lib = lib
     return lib

@@ -807,6 +807,20 @@ __device__ __forceinline__ uint32_t node_draw(uint32_t slo, uint32_t shi, uint32
   return lowbias32(lowbias32(lowbias32(update * 0x85EBCA6BU + shi) ^ (uint32_t)node ^ salt) +
                    (uint32_t)(node >> 32) + slo);
 }
+// the word of cell `cell` (its global id, below 2^32) in the population event
+// `key` (avida_amd/popevents.py event_draw): stateless like
+// node_draw, no organism's stream moves.  event_base is the part every cell of
+// an event shares (the host computes it once); lowbias32 is a bijection, so
+// within one event no two cells draw the same word.
+#define SALT_EVENT 0x0E7E47D5u
+__host__ __device__ __forceinline__ uint32_t event_base(uint32_t slo, uint32_t shi, uint64_t key) {
+  const uint32_t a = lowbias32((uint32_t)(key >> 32) * 0x85EBCA6BU + shi);
+  const uint32_t b = lowbias32(a ^ (uint32_t)key ^ SALT_EVENT);
+  return lowbias32(b + slo);
+}
+__host__ __device__ __forceinline__ uint32_t event_draw(uint32_t base, uint64_t cell) {
+  return lowbias32(base ^ (uint32_t)cell);
+}
 // a merit the scheduler can weigh: finite and not negative (NaN, -x and inf
 // are never scheduled; large finite merits of multiplicative environments are)
 __device__ __forceinline__ bool merit_ok(double m) { return m >= 0.0 && m <= 1.7976931348623157e308; }
@@ -1218,3 +1232,31 @@ void launch_cell_dist(const DevWorld& W, const DistScratch& S, hipStream_t s, in
                       int ref_len, bool want_ham, bool want_edit);
 // S.hist and S.living zeroed by the caller
 void launch_site_hist(const DevWorld& W, const DistScratch& S, hipStream_t s, int64_t first, int64_t count);
+// population events (popevents.hip): kills decided on the device.
+// A killed cell loses CTL_ALIVE and nothing else (avgpu_kill).  EvScratch: the
+// world's scratch, one allocation; the caller zeroes killed, sel and hist
+// (EV_ZERO_BYTES from killed) before a launch.
+#define EV_DIGIT_BITS 8                     // the select's digit: four passes over a 32-bit word
+#define EV_BINS (1 << EV_DIGIT_BITS)
+#define EV_PASSES (32 / EV_DIGIT_BITS)
+struct EvSelect {
+  uint32_t prefix;          // the digits of the threshold chosen so far (high bits)
+  uint32_t kill_all;        // keep == 0
+  uint64_t rank;            // the rank still looked for among the words with that prefix, 1-based;
+                            // 0: no threshold (keep >= living), nobody dies
+};
+struct EvScratch {
+  unsigned long long* killed;   // the living organisms the call killed
+  EvSelect* sel;
+  uint32_t* hist;           // [EV_PASSES][EV_BINS] the select's digit counts
+  const int64_t* cells;     // [n] avgpu_kill_cells' ids
+  const uint64_t* keys;     // [nkeys] avgpu_kill_genotypes' keys, ascending, distinct
+};
+#define EV_ZERO_BYTES (16 + sizeof(EvSelect) + sizeof(uint32_t) * EV_PASSES * EV_BINS)
+void launch_kill_cells(const DevWorld& W, const EvScratch& S, hipStream_t s, int64_t n);
+// every living cell with event_draw(base, cell) < th dies; nkeys >= 0: only those whose gkey is among S.keys
+void launch_kill_prob(const DevWorld& W, const EvScratch& S, hipStream_t s, uint32_t base, uint64_t th, int64_t nkeys);
+// rows y1 .. y2, columns x1 .. x2 of the torus, as cActionKillRectangle's loops walk them (0 <= x1 <= x2 < x1 + X)
+void launch_kill_rect(const DevWorld& W, const EvScratch& S, hipStream_t s, int x1, int y1, int x2, int y2);
+// the living cells with the `keep` smallest words survive
+void launch_keep_sample(const DevWorld& W, const EvScratch& S, hipStream_t s, uint32_t base, int64_t keep);

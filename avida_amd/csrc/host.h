@@ -286,6 +286,17 @@ struct avgpu_world {
   avh::Event ev_dist[2];
   double dist_ms = 0.0;
   int64_t dist_pairs = 0, dist_cells = 0;
+  // population events (avgpu_kill_cells .. avgpu_keep_sample; popevents.hip):
+  // pev views the buffers, each allocated at its first use
+  EvScratch pev = {};
+  avh::DevBuf<unsigned long long> pev_ctr;  // the killed count, the select's state and histograms (EV_ZERO_BYTES)
+  avh::DevBuf<uint64_t> pev_in;             // a call's cell ids or genotype keys, grown by 1.25x
+  avh::PinnedBuf<uint64_t> pev_host;        // ... and the pinned words they are uploaded from
+  int64_t pev_in_cap = 0;
+  avh::Event ev_pev[2];                     // around the last call's kernels
+  avh::Event ev_pev_up;                     // the last upload from pev_host
+  bool pev_timed = false;
+  int64_t pev_cells = 0;
 
   // the one way to make an array that lives as long as the world: zero-filled
   // in stream order, freed with the world

@@ -19,7 +19,13 @@ path is relative to the config directory), SaveCheckpoint [file] /
 LoadCheckpoint <file> (full hardware state, avida_amd/checkpoint.py;
 after LoadCheckpoint the driver's update counter is the checkpoint's, so the
 next update processed is the one after it and later events fire by that
-numbering, as LoadPopulation's update argument does), Exit.  Other Print* events write nothing; anything else is an error.
+numbering, as LoadPopulation's update argument does), the population events
+of avida_amd/popevents.py -- KillProb / KillRate [p = 0.9], KillRectangle
+[x1 y1 x2 y2 = 0], ApplyBottleneck [size = 100], SerialTransfer [size = 1]
+[ignore_deads = 1], KillDominantGenotype, KillProbSequence <sequence>
+[p = 0.9]; each draws with the key (update << 32) | index of its line among
+the events -- and Exit.  Other Print* events write nothing; anything else is
+an error.
 
     python -m avida_amd.driver -c <config dir> -d <data dir> [-u MAX_UPDATES]
 """
@@ -30,7 +36,7 @@ import ctypes as C
 import os
 import sys
 
-from . import capi, checkpoint, datafiles, distance, files, population, systematics
+from . import capi, checkpoint, datafiles, distance, files, popevents, population, systematics
 
 
 class ProductWorld:
@@ -155,6 +161,28 @@ class ProductWorld:
         of the living organisms (avgpu_site_histogram)"""
         return distance.site_histogram(self, first, count)
 
+    def kill_cells(self, cells):
+        """kill the listed cells on the device (avgpu_kill_cells); like the
+        four below it returns the living organisms killed"""
+        return popevents.kill_cells(self, cells)
+
+    def kill_prob(self, p, key):
+        """every organism dies with probability p (avgpu_kill_prob; KillProb)"""
+        return popevents.apply_kill_prob(self, p, key)
+
+    def kill_rect(self, x1=0, y1=0, x2=0, y2=0):
+        """KillRectangle's raw arguments (avgpu_kill_rect)"""
+        return popevents.apply_kill_rect(self, x1, y1, x2, y2)
+
+    def kill_genotypes(self, keys, p, key):
+        """the organisms of the listed genotype keys die with probability p (avgpu_kill_genotypes)"""
+        return popevents.apply_kill_genotypes(self, keys, p, key)
+
+    def keep_sample(self, keep, key):
+        """a uniform sample of `keep` organisms survives (avgpu_keep_sample;
+        SerialTransfer, ApplyBottleneck)"""
+        return popevents.apply_keep_sample(self, keep, key)
+
     def resources(self, spatial=False):
         lv = (C.c_double * max(1, self.nres))()
         self._call("get_resources", self.h, lv, None)
@@ -212,7 +240,8 @@ class Driver:
         self.data_dir = data_dir
         # genotype classification runs every update when a data file needs it
         # (the reference's systematics manager classifies every birth)
-        need = {"PrintCountData", "PrintDominantData", "SavePopulation", "PrintAverageData", *distance.Actions.NAMES}
+        need = {"PrintCountData", "PrintDominantData", "SavePopulation", "PrintAverageData", *distance.Actions.NAMES,
+                "KillDominantGenotype"}
         # (on the device where the world keeps the arbiter there, else on the host)
         kind = systematics.DeviceGenotypeArbiter if hasattr(self.world, "classify_genotypes") \
             else systematics.GenotypeArbiter
@@ -231,6 +260,8 @@ class Driver:
         self.dist = distance.Actions(self.world, self.iset, data_dir, config_dir)
         self.done = False
         self.update = -1
+        self.event_index = 0          # the line, among the events, of the event being run
+        self.unsequenced = 0          # genotypes SerialTransfer's "ignore deads" left alone (_population_event)
 
     def _org(self, name):
         return files.read_org(os.path.join(self.config_dir, name), self.iset)
@@ -246,8 +277,54 @@ class Driver:
         table, totals = w.genotypes() if hasattr(w, "genotypes") else systematics.table_from_census(w.census())
         self.arbiter.update_table(table, totals, max(self.update, 0))
 
+    POPULATION_EVENTS = ("KillProb", "KillRate", "KillRectangle", "ApplyBottleneck", "SerialTransfer",
+                         "KillDominantGenotype", "KillProbSequence")
+
+    def _population_event(self, action, args):
+        """The population actions of actions/PopulationActions.cc through
+        avida_amd/popevents.py: on the device where the world decides them
+        there, else from the census, cell by cell.  The event's draws are keyed
+        by (update << 32) | index of its line among the events.
+        SerialTransfer with ignore_deads first kills the genotypes whose test
+        fitness is 0 (cPopulation::SerialTransfer, main/cPopulation.cc:
+        7559-7564), from the sequences of the living genotypes obtained as
+        population.save_population obtains them; a genotype without a sequence
+        (every member has copied into its own first sites) is left alone, and
+        self.unsequenced counts them."""
+        w = self.world
+        key = (max(self.update, 0) << 32) | self.event_index
+        if action in ("KillProb", "KillRate"):               # :1171-1175; KillRate is its alias (:5743)
+            popevents.apply_kill_prob(w, float(args[0]) if args else 0.9, key)
+        elif action == "KillRectangle":                      # :1762-1768
+            popevents.apply_kill_rect(w, *[int(a) for a in args[:4]])
+        elif action == "ApplyBottleneck":                    # :1200-1204 (a negative size never ends there)
+            popevents.apply_keep_sample(w, max(int(args[0]) if args else 100, 0), key)
+        elif action == "SerialTransfer":                     # :1839-1846
+            size = int(args[0]) if args else 1
+            ignore_deads = int(args[1]) if len(args) > 1 else 1
+            if size < 0:
+                size = 1
+            if ignore_deads:
+                dead, unsequenced = popevents.dead_genotype_keys(w, self.iset)
+                self.unsequenced += unsequenced
+                popevents.apply_kill_genotypes(w, dead, 1.0, key)
+            popevents.apply_keep_sample(w, size, key)
+        elif action == "KillDominantGenotype":               # :1240-1256
+            best = self.arbiter.best_key
+            if best is not None:
+                popevents.apply_kill_genotypes(w, [int(best)], 1.0, key)
+        elif action == "KillProbSequence":                   # :1268-1273
+            genome = self.iset.parse_sequence(args[0])
+            gkey = systematics.genome_key(bytes(self.iset.handlers[x] for x in genome))
+            popevents.apply_kill_genotypes(w, [gkey], float(args[1]) if len(args) > 1 else 0.9, key)
+        if self.arbiter is not None:          # the survivors are classified at once, as after injections
+            self._classify()
+
     def _action(self, action, args):
         w = self.world
+        if action in self.POPULATION_EVENTS:
+            self._population_event(action, args)
+            return
         if action == "Inject":
             cell = int(args[1]) if len(args) > 1 else 0
             merit = float(args[2]) if len(args) > 2 else -1.0
@@ -318,8 +395,9 @@ class Driver:
             raise ValueError(f"event action {action!r} is not supported on this path")
 
     def run(self, max_updates=None):
-        for trig, start, action, args in self.events:
+        for i, (trig, start, action, args) in enumerate(self.events):
             if start.split(":")[0] == "begin":
+                self.event_index = i
                 self._action(action, args)
         while not self.done and (max_updates is None or self.update + 1 < max_updates):
             self.update += 1
@@ -328,8 +406,9 @@ class Driver:
             self.rec.end_update(self.world.run_update())
             if self.arbiter is not None:
                 self._classify()
-            for trig, start, action, args in self.events:
+            for i, (trig, start, action, args) in enumerate(self.events):
                 if _fires(trig, start, self.update):
+                    self.event_index = i
                     self._action(action, args)
         self.rec.close()
         self.dist.close()

@@ -942,6 +942,61 @@ int avgpu_site_histogram(avgpu_world* w, int64_t first_cell, int64_t count, int3
  * (avgpu_cell_distances and avgpu_site_histogram, else 0). */
 int avgpu_last_distance_ms(avgpu_world* w, double* device_ms, int64_t* pairs, int64_t* cells);
 
+/* ---- population events -------------------------------------
+ * The kills an experiment schedules beside its Print and Save actions
+ * (actions/PopulationActions.cc), decided on the device.
+ * Effect on a cell: a killed cell is left exactly as avgpu_kill leaves it --
+ * its alive bit cleared, nothing else written; each call equals avgpu_kill
+ * over the same set of cells.  Statistics are unchanged ("deaths" stays the
+ * old-age deaths).
+ * Draws: stateless.  From the world's seed, the caller's 64-bit
+ * `key` and a cell's global id the event gives the cell one 32-bit word h,
+ * u = h / 2^32; no organism's random stream moves.  Within one event no two
+ * cells draw the same h.  A world of 2^32 cells or more: AVGPU_EUNSUPPORTED
+ * from the calls that draw or index a cell by 32 bits (avgpu_kill_prob,
+ * avgpu_kill_rect, avgpu_kill_genotypes, avgpu_keep_sample).
+ * Ordering and return: the calls are stream-ordered behind the queued
+ * updates.  killed == NULL: the call does not wait for the device (a call
+ * that uploads ids or keys waits for the previous such upload only).  killed
+ * != NULL: the call completes and stores the number of living organisms it
+ * killed (one 8-byte read).  On any error the world is unchanged and *killed
+ * untouched.
+ * Ownership: the scratch belongs to the world and goes with avgpu_destroy.
+ * A strip tile: AVGPU_EUNSUPPORTED naming the call (the rectangle and the
+ * sample are global). */
+/* A loop of cPopulation::KillOrganism: ids in any order, duplicates allowed;
+ * killed counts the distinct living victims.  AVGPU_EINVAL, checked before
+ * anything is queued: an id outside the world, n < 0 or above 2^31, NULL
+ * cells with n > 0. */
+int avgpu_kill_cells(avgpu_world* w, const int64_t* cells, int64_t n, int64_t* killed);
+/* KillProb / KillRate (:1166-1187): every living cell with u < p dies.
+ * AVGPU_EINVAL: p outside [0, 1] or NaN. */
+int avgpu_kill_prob(avgpu_world* w, double p, uint64_t key, int64_t* killed);
+/* KillRectangle (:1754-1815) with the raw arguments; the library restates the
+ * constructor (:1770-1798): each coordinate clamped to [0, dim - 1], then
+ * x2 += WORLD_X if x2 < x1, y2 += WORLD_Y if y2 < y1; the cells are
+ * (i % WORLD_Y) * WORLD_X + (j % WORLD_X) for i in y1..y2, j in x1..x2. */
+int avgpu_kill_rect(avgpu_world* w, int x1, int y1, int x2, int y2, int64_t* killed);
+/* Every living cell whose genotype key (avgpu_census.genotype_key) is among
+ * `keys` (any order, duplicates allowed) dies with probability p, from the
+ * draw avgpu_kill_prob makes with the same key: KillDominantGenotype
+ * (:1226-1258, p = 1), KillProbSequence (:1261-1299), the "ignore deads" leg
+ * of SerialTransfer.  nkeys == 0 kills nothing.  AVGPU_EINVAL: p as above,
+ * nkeys < 0, NULL keys with nkeys > 0. */
+int avgpu_kill_genotypes(avgpu_world* w, const uint64_t* keys, int64_t nkeys, double p, uint64_t key, int64_t* killed);
+/* SerialTransfer's removal loop (main/cPopulation.cc:7577-7584) and
+ * ApplyBottleneck (:1195-1224): exactly min(keep, living) organisms survive,
+ * the living cells with the `keep` smallest h -- a uniform sample without
+ * replacement, as the reference's swap-remove and rejection draws leave.
+ * keep >= living writes nothing, keep == 0 kills everyone.  AVGPU_EINVAL:
+ * keep < 0. */
+int avgpu_keep_sample(avgpu_world* w, int64_t keep, uint64_t key, int64_t* killed);
+/* Timing of the last of the five calls above (no reference equivalent): waits
+ * for it, then the device time of its kernels in ms (HIP events on the
+ * world's stream) and the control words they read (every pass of the sample
+ * counted).  Zeros before the first such call. */
+int avgpu_last_event_ms(avgpu_world* w, double* device_ms, int64_t* cells_scanned);
+
 /* ---- statistics / multi-GPU plumbing ------------------------------------ */
 /* the last update's statistics (reduced here if that update ran with out == NULL) */
 int avgpu_get_stats(avgpu_world* w, avgpu_update_stats* out);
