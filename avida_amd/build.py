@@ -21,8 +21,8 @@ SOURCES = [# the interpreter's kernels (csrc/interp_launch.h), by far the longes
            "resources.hip", "genotypes.hip", "arbiter.hip", "lineage.hip", "landscape.hip", "distance.hip",
            "popevents.hip",
            # the host side of the C ABI, one file per subsystem (csrc/host.h is what they share)
-           "capi.hip", "capi_serial.hip", "capi_systematics.hip", "capi_state.hip", "capi_landscape.hip",
-           "capi_distance.hip", "capi_popevents.hip", "capi_resources.hip", "capi_tiles.hip"]
+           "capi.hip", "capi_serial.hip", "capi_systematics.hip", "capi_lineage.hip", "capi_state.hip",
+           "capi_landscape.hip", "capi_distance.hip", "capi_popevents.hip", "capi_resources.hip", "capi_tiles.hip"]
 OUT = os.path.join(HERE, "libavida_gpu.so")
 # diagnostic variant with per-phase s_memtime clocks (tools/phase_clocks.py only)
 OUT_CLK = os.path.join(HERE, "libavida_gpu_clk.so")

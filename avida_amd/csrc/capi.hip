@@ -555,7 +555,7 @@ int avgpu_destroy(avgpu_world* w) {
   if (!w) return 0;
   if (w->stream) hipStreamSynchronize(w->stream);
   if (w->own_stream.get()) hipStreamSynchronize(w->own_stream.get());
-  if (w->land) avgpu_destroy(w->land);
+  if (w->land.world) avgpu_destroy(w->land.world);
   delete w;
   return 0;
 }

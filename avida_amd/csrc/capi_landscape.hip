@@ -8,23 +8,21 @@ extern "C" {
 int avgpu_test_genomes(avgpu_world* w, int n, const uint8_t* genomes, const int32_t* lens,
                        avgpu_test_result* results, char* executed_flags, int flags_cap,
                        uint8_t* offspring) {
-  int rc = ready(w);
-  if (rc < 0) return rc;
+  RCCHK(ready(w));
   if (n <= 0) return 0;
   avgpu_cfg tc = w->cfg;
   tc.copy_mut_prob = 0; tc.divide_mut_prob = 0; tc.divide_ins_prob = 0; tc.divide_del_prob = 0;
   avgpu_world* t = create_world(&tc, w->device, n, true);
   if (!t) return AVGPU_ENOMEM;
-  if ((rc = copy_tables(t, w)) < 0) { avgpu_destroy(t); return rc; }
-  if ((rc = set_orgs_impl(t, 0, n, genomes, lens, nullptr, nullptr, 1)) < 0) { avgpu_destroy(t); return rc; }
+  struct Destroy { avgpu_world* t; ~Destroy() { avgpu_destroy(t); } } destroy{t};   // on every return
+  RCCHK(copy_tables(t, w));
+  RCCHK(set_orgs_impl(t, 0, n, genomes, lens, nullptr, nullptr, 1));
   std::vector<int32_t> budget(n);
   for (int i = 0; i < n; i++) budget[i] = w->cfg.test_cpu_time_mod * lens[i];
-  if ((rc = avgpu_step(t, 0, n, budget.data(), 0, AVGPU_MODE_TEST)) < 0) { avgpu_destroy(t); return rc; }
+  RCCHK(avgpu_step(t, 0, n, budget.data(), 0, AVGPU_MODE_TEST));
   std::vector<avgpu_cpu_state> st(n);
   std::vector<uint8_t> ops((size_t)n * AVGPU_MAX_GENOME), fl((size_t)n * AVGPU_MAX_GENOME);
-  if ((rc = avgpu_get_states(t, 0, n, st.data(), ops.data(), fl.data(), AVGPU_MAX_GENOME)) < 0) {
-    avgpu_destroy(t); return rc;
-  }
+  RCCHK(avgpu_get_states(t, 0, n, st.data(), ops.data(), fl.data(), AVGPU_MAX_GENOME));
   std::vector<uint8_t> tflags((size_t)n * TAPE_SLOT), tchild((size_t)n * TAPE_SLOT);
   std::vector<int32_t> tflen(n), tclen(n);
   // (checked: a failed copy would hand back uninitialised flags and offspring)
@@ -35,10 +33,7 @@ int avgpu_test_genomes(avgpu_world* w, int n, const uint8_t* genomes, const int3
       hipMemcpyAsync(tclen.data(), t->W.t_child_len, n * 4, hipMemcpyDeviceToHost, t->stream)};
   const hipError_t se = hipStreamSynchronize(t->stream);
   for (hipError_t e : {ce[0], ce[1], ce[2], ce[3], se})
-    if (e != hipSuccess) {
-      avgpu_destroy(t);
-      return fail(AVGPU_EHIP, std::string("test_genomes copy: ") + hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(AVGPU_EHIP, std::string("test_genomes copy: ") + hipGetErrorString(e));
   size_t off = 0;
   for (int i = 0; i < n; i++) {
     avgpu_test_result& r = results[i];
@@ -77,21 +72,21 @@ int avgpu_test_genomes(avgpu_world* w, int n, const uint8_t* genomes, const int3
     }
     off += lens[i];
   }
-  avgpu_destroy(t);
   return 0;
 }
 
 // ---- mutational landscapes (landscape.hip) ----
-// the scratch test world and the per-chunk scratch, for the current land_chunk
+// the scratch test world and the view's per-chunk scratch, for the current chunk
 static int land_alloc(avgpu_world* w) {
-  if (w->land && w->land_s.chunk == w->land_chunk) return 0;
-  if (w->land) {
-    avgpu_destroy(w->land);
-    w->land = nullptr;
+  Landscapes& D = w->land;
+  if (D.world && D.view.chunk == D.chunk) return 0;
+  if (D.world) {
+    avgpu_destroy(D.world);
+    D.world = nullptr;
   }
   avgpu_cfg tc = w->cfg;     // the test CPU: mutations off (as avgpu_test_genomes)
   tc.copy_mut_prob = 0; tc.divide_mut_prob = 0; tc.divide_ins_prob = 0; tc.divide_del_prob = 0;
-  const int64_t n = w->land_chunk;
+  const int64_t n = D.chunk;
   avgpu_world* t = create_world(&tc, w->device, n, true);
   if (!t) return AVGPU_ENOMEM;
   t->time_every = 0;         // its interpreter phases are not bracketed: the call times itself
@@ -107,14 +102,13 @@ static int land_alloc(avgpu_world* w) {
     rc = t->alloc(&S.gen[d], (size_t)n * TAPE_SLOT);
   }
   if (rc == 0 && hipStreamSynchronize(t->stream) != hipSuccess) rc = fail(AVGPU_EHIP, "landscape scratch");
-  for (Event& e : w->ev_land)
-    if (rc == 0) rc = e.create();      // (once: they outlive the scratch world)
+  if (rc == 0) rc = D.timer.create();  // (once: it outlives the scratch world)
   if (rc < 0) {
     avgpu_destroy(t);                  // (leaves the error string alone)
     return rc;
   }
-  w->land = t;
-  w->land_s = S;
+  D.world = t;
+  D.view = S;
   return 0;
 }
 
@@ -122,15 +116,15 @@ int avgpu_set_landscape_chunk(avgpu_world* w, int64_t cells) {
   if (!w) return fail(AVGPU_EINVAL, "NULL world");
   if (cells <= 0 || cells % LAND_TILE != 0 || cells > (1ll << 30))
     return fail(AVGPU_EINVAL, "landscape chunk: a positive multiple of 256 cells, at most 2^30");
-  w->land_chunk = cells;      // the scratch world follows at the next avgpu_landscapes
+  w->land.chunk = cells;      // the scratch world follows at the next avgpu_landscapes
   return 0;
 }
 
 int avgpu_last_landscape_ms(avgpu_world* w, double* device_ms, int64_t* mutants, int64_t* gestations) {
   if (!w) return fail(AVGPU_EINVAL, "NULL world");
-  if (device_ms) *device_ms = w->land_ms;
-  if (mutants) *mutants = w->land_mutants;
-  if (gestations) *gestations = w->land_runs;
+  if (device_ms) *device_ms = w->land.ms;
+  if (mutants) *mutants = w->land.mutants;
+  if (gestations) *gestations = w->land.runs;
   return 0;
 }
 
@@ -211,8 +205,8 @@ static int land_call(avgpu_world* w, const char* who, int n, const uint8_t* geno
   if ((rc = lay_out(mode, nullptr)) < 0) return rc;
   int64_t total = mut_off[n], tiles = tile_off[n];
   if ((rc = land_alloc(w)) < 0) return rc;
-  avgpu_world* t = w->land;
-  LandScratch S = w->land_s;
+  avgpu_world* t = w->land.world;
+  LandScratch S = w->land.view;
   // the scratch world runs in this world's stream order, with its tables
   t->stream = w->stream;
   struct Restore { avgpu_world* t; ~Restore() { t->stream = t->own_stream.get(); } } restore{t};
@@ -299,7 +293,7 @@ static int land_call(avgpu_world* w, const char* who, int n, const uint8_t* geno
     }
     return 0;
   };
-  HIPCHK(hipEventRecord(w->ev_land[0], w->stream));
+  RCCHK(w->land.timer.start(w->stream));
   for (int64_t m0 = 0; m0 < n; m0 += S.chunk)
     if ((rc = run_chunk(LAND_BASE, m0, (int)std::min<int64_t>(S.chunk, n - m0))) < 0) return rc;
   runs = 0;                                  // (the base genomes' runs are not the landscape's)
@@ -323,7 +317,7 @@ static int land_call(avgpu_world* w, const char* who, int n, const uint8_t* geno
     launch_land_epi_rows(S, w->stream);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipEventRecord(w->ev_land[1], w->stream));
+  RCCHK(w->land.timer.stop(w->stream));
   std::vector<avgpu_landscape> rows((size_t)n);
   std::vector<avgpu_epistasis> erows(epi ? (size_t)n : 0);
   std::vector<int32_t> sc(epi ? 0 : (size_t)sites);
@@ -335,11 +329,9 @@ static int land_call(avgpu_world* w, const char* who, int n, const uint8_t* geno
   if (fitness_chart)
     HIPCHK(hipMemcpyAsync(chart.data(), S.chart, chart.size() * sizeof(double), hipMemcpyDeviceToHost, w->stream));
   HIPCHK(hipStreamSynchronize(w->stream));
-  float ms = 0.f;
-  HIPCHK(hipEventElapsedTime(&ms, w->ev_land[0], w->ev_land[1]));
-  w->land_ms = ms;
-  w->land_mutants = total;
-  w->land_runs = runs;
+  RCCHK(w->land.timer.elapsed(&w->land.ms));
+  w->land.mutants = total;
+  w->land.runs = runs;
   // cLandscape::Process (main/cLandscape.cc:158-169): a site's entropy is the
   // log of its legal states, the unmutated one included (ProcessInsert,
   // ProcessDelete and TestAllPairs compute none); ProcessDump's and

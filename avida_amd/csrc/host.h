@@ -1,11 +1,11 @@
 // host.h -- what the C-API translation units (capi*.hip) share.  Host only:
 // nothing that holds a kernel includes it.
 //
-// Ownership: locals and members own, through the four scoped types below; the
-// structs a launch takes by value (DevWorld, GtScratch, ArbScratch,
-// LandScratch: device.h) only view, and are assigned from the owners where a
-// buffer is (re)allocated.  avgpu_world::alloc makes the arrays that live as
-// long as the world.
+// Ownership: locals and members own, through the scoped types below; the
+// structs a launch takes by value (DevWorld, the *Scratch views: device.h) only
+// view.  Each on-demand subsystem keeps its state in one struct (GenotypeTable
+// .. PopEvents), and one function per subsystem writes its view from the
+// owners.  avgpu_world::alloc makes the arrays that live as long as the world.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "device.h"
+#include "grow.h"
 
 // (hidden: the helpers cross the library's files, not its boundary)
 namespace avh __attribute__((visibility("hidden"))) {
@@ -42,6 +43,8 @@ inline int fail(int code, const std::string& msg) {
     hipError_t _e = (x);                                                            \
     if (_e != hipSuccess) return fail(AVGPU_EHIP, std::string(#x ": ") + hipGetErrorString(_e)); \
   } while (0)
+// (a call that returns one of the library's own codes)
+#define RCCHK(x) do { const int _rc = (x); if (_rc < 0) return _rc; } while (0)
 // A copy / fill of an API call on the world's stream, complete on return.  The
 // world's streams are non-blocking: a null-stream hipMemcpy / hipMemset would
 // neither wait for the kernels queued on them nor be waited for by them.
@@ -60,37 +63,58 @@ inline int fail(int code, const std::string& msg) {
 // (avgpu_live_objects)
 inline std::atomic<int64_t> g_live{0};
 
-// One hipMalloc.  A temporary that queued work reads is made with that work's
-// stream: the stream is synchronised before the buffer is freed, so no return
-// path, an early one included, frees under a running kernel.  A member is made
-// without one: whoever replaces it, and avgpu_destroy, synchronise first.
+// One hipMalloc, and the elements it has room for.  A temporary that queued
+// work reads is made with that work's stream: the stream is synchronised before
+// the buffer is freed, so no return path, an early one included, frees under a
+// running kernel.  A member is made without one and grows by reserve.
 template <typename T>
 class DevBuf {
  public:
   DevBuf() = default;
   explicit DevBuf(hipStream_t s) : stream_(s), sync_(true) {}
-  DevBuf(DevBuf&& o) noexcept : p_(o.p_), stream_(o.stream_), sync_(o.sync_) { o.p_ = nullptr; }
+  DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_), stream_(o.stream_), sync_(o.sync_) { o.p_ = nullptr; o.cap_ = 0; }
   // the buffers change hands, each side keeps its stream: what this held goes with o
-  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); return *this; }
+  DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
   ~DevBuf() { reset(); }
   int alloc(size_t count) {
     reset();
     hipError_t e = hipMalloc((void**)&p_, std::max<size_t>(count * sizeof(T), 16));
     if (e != hipSuccess) { p_ = nullptr; return fail(AVGPU_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e)); }
     g_live++;
+    cap_ = (int64_t)count;
+    return 0;
+  }
+  // Room for `need` elements: a buffer of grown_capacity(need, g), the first
+  // `keep` copied over on `s`.  The new buffer is the local nb until it is
+  // complete; after the swap nb holds the old one, and nb's destructor
+  // synchronises `s` before it frees it (work queued on `s` may still read it).
+  // On a failure nothing has changed.  Buffers that grow together follow the
+  // same steps by hand (arbiter_reserve).
+  int reserve(hipStream_t s, int64_t need, const Growth& g = {}, int64_t keep = 0) {
+    if (need <= cap_) return 0;
+    DevBuf nb(s);
+    RCCHK(nb.alloc((size_t)grown_capacity(need, g)));
+    if (keep > 0) {
+      HIPCHK(hipMemcpyAsync(nb.p_, p_, (size_t)keep * sizeof(T), hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipStreamSynchronize(s));
+    }
+    *this = std::move(nb);
     return 0;
   }
   T* get() const { return p_; }
+  int64_t capacity() const { return cap_; }
   void reset() {
     if (!p_) return;
     if (sync_) hipStreamSynchronize(stream_);
     hipFree(p_);
     g_live--;
     p_ = nullptr;
+    cap_ = 0;
   }
 
  private:
   T* p_ = nullptr;
+  int64_t cap_ = 0;
   hipStream_t stream_ = nullptr;
   bool sync_ = false;
 };
@@ -142,6 +166,26 @@ class Event {
   hipEvent_t e_ = nullptr;
 };
 
+// The event pair around a call's kernels, and the device time between them.
+class EventTimer {
+ public:
+  int create() { RCCHK(t0_.create()); return t1_.create(); }   // (once, like Event::create)
+  int start(hipStream_t s) { HIPCHK(hipEventRecord(t0_, s)); return 0; }
+  int stop(hipStream_t s) { HIPCHK(hipEventRecord(t1_, s)); return 0; }
+  // the stream has been synchronised since stop ...
+  int elapsed(double* ms) const {
+    float f = 0.f;
+    HIPCHK(hipEventElapsedTime(&f, t0_, t1_));
+    *ms = f;
+    return 0;
+  }
+  // ... or has not: waits for the stop event alone
+  int wait_elapsed(double* ms) const { HIPCHK(hipEventSynchronize(t1_)); return elapsed(ms); }
+
+ private:
+  Event t0_, t1_;
+};
+
 // One hipStream_t.
 class Stream {
  public:
@@ -160,9 +204,73 @@ class Stream {
   hipStream_t s_ = nullptr;
 };
 
+// ---- the on-demand subsystems: view, buffers, timers,
+// counters.  Nothing is allocated before a subsystem's first call. ----
+struct GenotypeTable {                 // avgpu_get_genotypes; the view's scratch is in the world's allocs
+  GtScratch view = {};
+  bool ready = false;
+  DevBuf<avgpu_genotype> rows;
+  EventTimer t_group, t_rows;
+  double ms = 0.0;
+  int64_t bytes = 0;
+};
+struct Arbiter {                       // avgpu_classify_genotypes: n rows of state, the last summary
+  ArbScratch view = {};
+  bool ready = false;
+  DevBuf<avgpu_arbiter_row> row[2];    // these five grow together (arbiter_reserve)
+  DevBuf<uint64_t> key[2];
+  DevBuf<avgpu_genotype> table;
+  PinnedBuf<avgpu_arbiter_summary> sum;   // view.h_sum: host-mapped
+  int64_t n = 0;
+  avgpu_arbiter_summary last = {};
+  EventTimer t_group, t_classify;
+  double ms = 0.0;
+  int64_t bytes = 0;
+};
+struct Lineage {                       // avgpu_enable_lineage
+  LinScratch view = {};
+  bool on = false;
+  DevBuf<avgpu_lineage_row> rows;
+  DevBuf<uint8_t> arena;
+  DevBuf<unsigned long long> ctr;
+  DevBuf<int64_t> idx, asz;            // the scratch: these four grow together
+  DevBuf<uint32_t> mark;
+  DevBuf<int32_t> newcell;
+  int64_t rows_hint = 0, arena_hint = 0, dropped = 0;
+  EventTimer t_classify, t_prune;
+  double classify_ms = 0.0, prune_ms = 0.0;
+};
+struct Landscapes {                    // avgpu_landscapes: the scratch test world of `chunk` cells
+  LandScratch view = {};
+  int64_t chunk = 65536;
+  avgpu_world* world = nullptr;        // made by the first call, again when chunk changes; avgpu_destroy frees it
+  EventTimer timer;
+  double ms = 0.0;
+  int64_t mutants = 0, runs = 0;
+};
+struct Distances {                     // avgpu_genome_distances .. avgpu_site_histogram
+  DistScratch view = {};
+  DevBuf<uint8_t> in;                  // the call's inputs: genomes, offsets, lengths, pairs
+  DevBuf<int32_t> out;                 // its results: hamming, then edit
+  DevBuf<int32_t> hist;                // the histogram, then the living count (8-B aligned)
+  EventTimer timer;
+  double ms = 0.0;
+  int64_t pairs = 0, cells = 0;
+};
+struct PopEvents {                     // avgpu_kill_cells .. avgpu_keep_sample
+  EvScratch view = {};
+  DevBuf<unsigned long long> ctr;      // the killed count, the select's state and histograms (EV_ZERO_BYTES)
+  DevBuf<uint64_t> in;                 // a call's cell ids or genotype keys ...
+  PinnedBuf<uint64_t> host;            // ... and the pinned words they are uploaded from: the two grow together
+  Event uploaded;                      // the last upload from host
+  EventTimer timer;                    // around the last call's kernels
+  bool timed = false;
+  int64_t cells = 0;
+};
+
 }  // namespace avh
 
-// Deleted by avgpu_destroy alone, which destroys the scratch world `land`
+// Deleted by avgpu_destroy alone, which destroys the scratch world `land.world`
 // first.  Then the destructor's body frees the allocs, and the members go in
 // reverse order of declaration: the buffers and events, own_stream last.
 struct avgpu_world {
@@ -229,75 +337,13 @@ struct avgpu_world {
   int last_k = 1;
   int tile_sub = 0, tile_k = 1, tile_sub_next = 0;
   uint32_t tile_key = 0;
-  // the genotype table (avgpu_get_genotypes): scratch allocated at the first
-  // call (in allocs), the row buffer grown to the largest table seen
-  GtScratch gt = {};
-  bool gt_ready = false;
-  avh::DevBuf<avgpu_genotype> gt_rows;
-  int64_t gt_rows_cap = 0;
-  avh::Event ev_gt[4];
-  double gt_ms = 0.0;
-  int64_t gt_bytes = 0;
-  // the device-resident genotype arbiter (avgpu_classify_genotypes): buffers
-  // allocated at the first use, grown with the row buffer's policy (arb views
-  // them); arb_n rows of state, arb_last the summary of the last
-  // classification (or set / reset)
-  ArbScratch arb = {};
-  avh::DevBuf<avgpu_arbiter_row> arb_row[2];
-  avh::DevBuf<uint64_t> arb_key[2];
-  avh::DevBuf<avgpu_genotype> arb_table;
-  avh::PinnedBuf<avgpu_arbiter_summary> arb_sum;   // arb.h_sum: host-mapped
-  bool arb_ready = false;
-  int64_t arb_n = 0;
-  avgpu_arbiter_summary arb_last = {};
-  avh::Event ev_arb[4];
-  double arb_ms = 0.0;
-  int64_t arb_bytes = 0;
-  // the lineage store (avgpu_enable_lineage; lineage.hip): lin is the view the
-  // launches take, assigned where a buffer is (re)allocated
-  bool lin_on = false;
-  LinScratch lin = {};
-  avh::DevBuf<avgpu_lineage_row> lin_rows;
-  avh::DevBuf<uint8_t> lin_arena;
-  avh::DevBuf<unsigned long long> lin_ctr;
-  avh::DevBuf<int64_t> lin_idx, lin_asz;
-  avh::DevBuf<uint32_t> lin_mark;
-  avh::DevBuf<int32_t> lin_newcell;
-  int64_t lin_rows_hint = 0, lin_arena_hint = 0, lin_dropped = 0;
-  avh::Event ev_lin[4];
-  double lin_ms = 0.0, lin_prune_ms = 0.0;
-  // mutational landscapes (avgpu_landscapes): the scratch test world of
-  // land_chunk cells the mutants run through and the per-chunk scratch (in its
-  // allocs), created by the first call, re-created when land_chunk changes
-  LandScratch land_s = {};
-  int64_t land_chunk = 65536;
-  avh::Event ev_land[2];
-  double land_ms = 0.0;
-  int64_t land_mutants = 0, land_runs = 0;
-  avgpu_world* land = nullptr;
-  // genetic distances and the consensus histogram (avgpu_genome_distances,
-  // avgpu_cell_distances, avgpu_site_histogram; distance.hip): dist views the
-  // buffers, each allocated at its first use and grown by 1.25x
-  DistScratch dist = {};
-  avh::DevBuf<uint8_t> dist_in;        // the call's inputs: genomes, offsets, lengths, pairs
-  avh::DevBuf<int32_t> dist_out;       // its results: hamming, then edit
-  avh::DevBuf<int32_t> dist_hist;      // the histogram, then the living count (8-B aligned)
-  int64_t dist_in_cap = 0, dist_out_cap = 0;
-  avh::Event ev_dist[2];
-  double dist_ms = 0.0;
-  int64_t dist_pairs = 0, dist_cells = 0;
-  // population events (avgpu_kill_cells .. avgpu_keep_sample; popevents.hip):
-  // pev views the buffers, each allocated at its first use
-  EvScratch pev = {};
-  avh::DevBuf<unsigned long long> pev_ctr;  // the killed count, the select's state and histograms (EV_ZERO_BYTES)
-  avh::DevBuf<uint64_t> pev_in;             // a call's cell ids or genotype keys, grown by 1.25x
-  avh::PinnedBuf<uint64_t> pev_host;        // ... and the pinned words they are uploaded from
-  int64_t pev_in_cap = 0;
-  avh::Event ev_pev[2];                     // around the last call's kernels
-  avh::Event ev_pev_up;                     // the last upload from pev_host
-  bool pev_timed = false;
-  int64_t pev_cells = 0;
-
+  // the on-demand subsystems (above)
+  avh::GenotypeTable gt;
+  avh::Arbiter arb;
+  avh::Lineage lin;
+  avh::Landscapes land;
+  avh::Distances dist;
+  avh::PopEvents pev;
   // the one way to make an array that lives as long as the world: zero-filled
   // in stream order, freed with the world
   template <typename T>
@@ -337,6 +383,9 @@ int drain_ring(avgpu_world* w, int keep);
 void after_resources_begin(avgpu_world* w);
 uint32_t step_key(const avgpu_world* w, int sub, int K);
 int choose_k(const avgpu_cfg& c, long long pred, long long n, bool handed_in, long long cnt);
+// capi_lineage.hip
+int lineage_step(avgpu_world* w, int64_t n_prev, int64_t id0, int64_t m, int64_t update);
+int lineage_clear(avgpu_world* w);
 // capi_serial.hip
 int reaper_read(avgpu_world* w, std::vector<int32_t>& q);
 int reaper_write(avgpu_world* w, const std::vector<int32_t>& q);

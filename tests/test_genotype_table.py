@@ -277,12 +277,12 @@ def _set_keys(b, keys):
     b._call("set_genotype_keys", b.h, 0, len(k), k.ctypes.data_as(C.c_void_p))
 
 
-def _populate(b, n, rng):
-    """one-instruction organisms in every cell, a seeded third killed, the
-    living given phenotype values (gestation times with zeros among them,
-    merits, fitnesses, sizes) through avgpu_set_states"""
+def _populate(b, n, rng, kill=True):
+    """one-instruction organisms in every cell, a seeded third killed (unless
+    kill is False), the living given phenotype values (gestation times with
+    zeros among them, merits, fitnesses, sizes) through avgpu_set_states"""
     b.set_orgs(0, [bytes([0])] * n)
-    dead = np.flatnonzero(rng.random(n) < 1.0 / 3.0)
+    dead = np.flatnonzero(rng.random(n) < 1.0 / 3.0) if kill else np.zeros(0, dtype=np.int64)
     for c in dead:
         b.kill(int(c))
     st = (capi.AvgpuCpuState * n)()
@@ -489,6 +489,34 @@ def test_gpu_table_sizing_and_refusals(golden):
     assert lib.avgpu_get_genotypes(t.h, None, 0, C.byref(tot)) == -5         # AVGPU_EUNSUPPORTED
     assert "genotype table on strip tiles" in lib.avgpu_last_error().decode()
     t.close()
+
+
+@pytest.mark.gpu
+def test_gpu_table_row_buffer_regrows(golden):
+    """1536 living cells.  8 genotypes, then every cell its own genotype: by
+    the size policy (held to literals in tests/test_host_growth.py; no call
+    reports a capacity, so not asserted here) the row buffer is made at its
+    floor of 1024 rows, and the second table's 1536 rows need a new one, cut to
+    a row per cell.  Asserted: both tables are the census's, and the library
+    owns as much after the second call as after the first -- a buffer
+    replaced, none added."""
+    n = 1536
+    rng = np.random.default_rng(1536)
+    b = _gpu(golden, n)
+    _populate(b, n, rng, kill=False)
+    counts = []
+    for pool in (8, n):
+        keys = rng.integers(1, 1 << 63, size=pool, dtype=np.uint64) * np.uint64(2) + np.uint64(1)
+        assert len(np.unique(keys)) == pool
+        _set_keys(b, keys[rng.permutation(n) % pool])
+        census = b.census()
+        assert (census["genotype_key"] != 0).all()
+        table, totals = _device_table(b)
+        assert len(table) == pool
+        check_table(table, totals, census)
+        counts.append(capi.live_objects(b.lib))
+    assert counts[1] == counts[0]
+    b.close()
 
 
 def _rows(path):

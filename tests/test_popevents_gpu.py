@@ -359,6 +359,37 @@ def test_calls_behind_queued_updates(golden):
         b.close()
 
 
+def test_kill_list_regrows_behind_queued_updates(golden):
+    """avgpu_kill_cells with 4 cells, then with 40, each right behind three
+    queued updates and nothing synchronised in between: the second list does
+    not fit the words made for the first (5 of them), so the call replaces the
+    device words and their pinned twin while updates are queued.  A twin that
+    waits for every update and kills the specification's sets cell by cell ends
+    alike, and the library owns as much after the second call as after the
+    first: buffers replaced, none added."""
+    a, b = tc._world("gpu", golden, "logic9"), tc._world("gpu", golden, "logic9")
+    try:
+        lib, h = a.lib, a.h
+        lists = [np.array([5, 17, 200, 513], dtype=np.int64),
+                 np.sort(np.random.default_rng(40).choice(a.ncells, 40, replace=False)).astype(np.int64)]
+        counts = []
+        for ids in lists:
+            for _ in range(3):
+                assert lib.avgpu_run_update(h, None) == 0          # queued: no statistics, no sync
+            assert lib.avgpu_kill_cells(h, ids.ctypes.data_as(C.c_void_p), len(ids), None) == 0, \
+                lib.avgpu_last_error().decode()
+            counts.append(capi.live_objects(lib))
+        for ids in lists:
+            for _ in range(3):
+                b.run_update()
+            assert popevents.kill_cells(b, ids, device=False) > 0  # the specification: the living among the list, one by one
+        assert (a.digests() == b.digests()).all()
+        assert counts[1] == counts[0]
+    finally:
+        a.close()
+        b.close()
+
+
 def test_driver_files_equal_the_oracle_run(golden, tmp_path, monkeypatch):
     """the driver run of test_popevents_spec on ProductWorld: the device decides
     the events, and the data files are the oracle run's, byte for byte"""
