@@ -180,9 +180,7 @@ def get_census(lib, prefix, handle, first, count):
     """Census rows (CENSUS_DTYPE) of cells first .. first+count-1 through
     {prefix}get_census (avgpu_ = the product, orc_ = the oracle)."""
     out = np.zeros(count, dtype=CENSUS_DTYPE)
-    rc = getattr(lib, prefix + "get_census")(handle, first, count, out.ctypes.data_as(C.c_void_p))
-    if rc < 0:
-        raise RuntimeError(f"{prefix}get_census: {getattr(lib, prefix + 'last_error')().decode()}")
+    call(lib, prefix, "get_census", handle, first, count, out.ctypes.data_as(C.c_void_p))
     return out
 
 
@@ -213,7 +211,7 @@ def get_genotypes(lib, handle):
         if rc >= 0:
             return out[:rc], totals
         if rc != -1 or totals.num_genotypes <= cap:      # not the "cap too small" refusal
-            raise RuntimeError(f"avgpu_get_genotypes: {lib.avgpu_last_error().decode()}")
+            check(lib, rc, name="get_genotypes")
         cap = lib._genotype_cap = int(totals.num_genotypes) + int(totals.num_genotypes) // 4 + 16
 
 
@@ -233,12 +231,6 @@ ARBITER_SUMMARY_DTYPE = np.dtype([("update", "<i8"), ("num_organisms", "<i8"), (
 assert ARBITER_SUMMARY_DTYPE.itemsize == 232
 
 
-def _arbiter_check(lib, rc, name):
-    if rc < 0:
-        raise RuntimeError(f"{name}: {lib.avgpu_last_error().decode()}")
-    return rc
-
-
 # one genotype of the lineage store (the ancestry
 # Systematics::Genotype keeps, systematics/Genotype.cc:139-176): rows ascending
 # by id, parent_id 0 = injected, -1 = orphan; seq_off the birth genome's offset
@@ -254,28 +246,24 @@ LINEAGE_SUMMARY_DTYPE = np.dtype([("rows", "<i8"), ("active_rows", "<i8"), ("are
 assert LINEAGE_SUMMARY_DTYPE.itemsize == 64
 
 
-def _chk(lib, rc, what):
-    if rc < 0:
-        msg = lib.avgpu_last_error()
-        raise RuntimeError(f"{what} ({rc}): {msg.decode() if msg else ''}")
-    return rc
+def _vp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def enable_lineage(lib, handle, on=True, rows_hint=0, arena_hint=0):
     """avgpu_enable_lineage: the lineage store beside the device arbiter"""
-    _chk(lib, lib.avgpu_enable_lineage(handle, int(bool(on)), int(rows_hint), int(arena_hint)), "avgpu_enable_lineage")
+    call(lib, "avgpu_", "enable_lineage", handle, int(bool(on)), int(rows_hint), int(arena_hint))
 
 
 def get_lineage(lib, handle, summary_only=False):
     """(rows, arena bytes, summary) of the store through avgpu_get_lineage"""
     s = np.zeros(1, dtype=LINEAGE_SUMMARY_DTYPE)
-    _chk(lib, lib.avgpu_get_lineage(handle, None, 0, None, 0, s.ctypes.data_as(C.c_void_p)), "avgpu_get_lineage")
+    call(lib, "avgpu_", "get_lineage", handle, None, 0, None, 0, _vp(s))
     if summary_only:
         return None, None, s[0]
     rows = np.zeros(int(s[0]["rows"]), dtype=LINEAGE_ROW_DTYPE)
     arena = np.zeros(max(1, int(s[0]["arena_bytes"])), dtype=np.uint8)
-    _chk(lib, lib.avgpu_get_lineage(handle, rows.ctypes.data_as(C.c_void_p), len(rows),
-                                     arena.ctypes.data_as(C.c_void_p), len(arena), None), "avgpu_get_lineage")
+    call(lib, "avgpu_", "get_lineage", handle, _vp(rows), len(rows), _vp(arena), len(arena), None)
     return rows, arena[:int(s[0]["arena_bytes"])], s[0]
 
 
@@ -283,14 +271,13 @@ def set_lineage(lib, handle, rows, arena, summary):
     rows = np.ascontiguousarray(rows, dtype=LINEAGE_ROW_DTYPE)
     arena = np.ascontiguousarray(arena, dtype=np.uint8)
     s = np.array([summary], dtype=LINEAGE_SUMMARY_DTYPE)
-    _chk(lib, lib.avgpu_set_lineage(handle, len(rows), rows.ctypes.data_as(C.c_void_p) if len(rows) else None,
-                                     arena.ctypes.data_as(C.c_void_p) if len(arena) else None, len(arena),
-                                     s.ctypes.data_as(C.c_void_p)), "avgpu_set_lineage")
+    call(lib, "avgpu_", "set_lineage", handle, len(rows), _vp(rows) if len(rows) else None,
+         _vp(arena) if len(arena) else None, len(arena), _vp(s))
 
 
 def prune_lineage(lib, handle):
     s = np.zeros(1, dtype=LINEAGE_SUMMARY_DTYPE)
-    _chk(lib, lib.avgpu_prune_lineage(handle, s.ctypes.data_as(C.c_void_p)), "avgpu_prune_lineage")
+    call(lib, "avgpu_", "prune_lineage", handle, _vp(s))
     return s[0]
 
 
@@ -298,8 +285,7 @@ def classify_genotypes(lib, handle, update, threshold):
     """One classification on the device (avgpu_classify_genotypes): its
     summary, one ARBITER_SUMMARY_DTYPE record"""
     out = np.zeros(1, dtype=ARBITER_SUMMARY_DTYPE)
-    _arbiter_check(lib, lib.avgpu_classify_genotypes(handle, int(update), int(threshold),
-                                                     out.ctypes.data_as(C.c_void_p)), "avgpu_classify_genotypes")
+    call(lib, "avgpu_", "classify_genotypes", handle, int(update), int(threshold), _vp(out))
     return out[0]
 
 
@@ -309,15 +295,12 @@ def get_arbiter(lib, handle, rows_hint=0):
     ascending, the summary record and the AVGPU_MAX_GENOME + 1 name counters"""
     summary = np.zeros(1, dtype=ARBITER_SUMMARY_DTYPE)
     sz = np.zeros(MAX_GENOME + 1, dtype=np.int64)
-    _arbiter_check(lib, lib.avgpu_get_arbiter(handle, None, None, 0, summary.ctypes.data_as(C.c_void_p),
-                                              sz.ctypes.data_as(C.c_void_p)), "avgpu_get_arbiter")
+    call(lib, "avgpu_", "get_arbiter", handle, None, None, 0, _vp(summary), _vp(sz))
     m = int(summary[0]["num_genotypes"])
     rows = np.zeros(m, dtype=ARBITER_ROW_DTYPE)
     table = np.zeros(m, dtype=GENOTYPE_DTYPE)
     if m:
-        rc = _arbiter_check(lib, lib.avgpu_get_arbiter(handle, rows.ctypes.data_as(C.c_void_p),
-                                                       table.ctypes.data_as(C.c_void_p), m, None, None),
-                            "avgpu_get_arbiter")
+        rc = call(lib, "avgpu_", "get_arbiter", handle, _vp(rows), _vp(table), m, None, None)
         assert rc == m
     return rows, table, summary[0], sz
 
@@ -329,10 +312,7 @@ def set_arbiter(lib, handle, rows, summary, sz_count):
     sz = None if sz_count is None else np.ascontiguousarray(sz_count, dtype=np.int64)
     if sz is not None and len(sz) != MAX_GENOME + 1:
         raise ValueError("sz_count holds AVGPU_MAX_GENOME + 1 counters")
-    _arbiter_check(lib, lib.avgpu_set_arbiter(handle, len(rows), rows.ctypes.data_as(C.c_void_p),
-                                              summary.ctypes.data_as(C.c_void_p),
-                                              None if sz is None else sz.ctypes.data_as(C.c_void_p)),
-                   "avgpu_set_arbiter")
+    call(lib, "avgpu_", "set_arbiter", handle, len(rows), _vp(rows), _vp(summary), _vp(sz))
 
 
 def live_objects(lib):
@@ -356,33 +336,6 @@ EPISTASIS_DTYPE = np.dtype([("total_epi_count", "<i8"), ("dead_epi_count", "<i8"
                             ("pos_epi_count", "<i8"), ("no_epi_count", "<i8"), ("gestations", "<i8", (3,)),
                             ("neg_epi_size", "<f8"), ("pos_epi_size", "<f8"), ("no_epi_size", "<f8")])
 assert EPISTASIS_DTYPE.itemsize == 88
-
-
-# C-ABI symbols declared in include/avida_gpu.h (checked by tests/test_capi.py)
-EXPORTED = [
-    "avgpu_last_error", "avgpu_cfg_defaults", "avgpu_check_cfg", "avgpu_create", "avgpu_destroy", "avgpu_sync",
-    "avgpu_load_instset", "avgpu_load_env", "avgpu_load_resources", "avgpu_get_resources",
-    "avgpu_set_resources", "avgpu_set_org", "avgpu_set_orgs", "avgpu_kill", "avgpu_set_states", "avgpu_set_clock",
-    "avgpu_step", "avgpu_run_update", "avgpu_run_updates", "avgpu_update_totals",
-    "avgpu_update_run", "avgpu_set_stream", "avgpu_get_states", "avgpu_get_census", "avgpu_set_genotype_keys",
-    "avgpu_test_genomes", "avgpu_get_stats", "avgpu_stats_vector", "avgpu_set_global_totals",
-    "avgpu_set_tile", "avgpu_tile_buffer_bytes", "avgpu_set_tile_buffers", "avgpu_tile_partials",
-    "avgpu_tile_begin", "avgpu_tile_steps", "avgpu_tile_begin_step", "avgpu_tile_place", "avgpu_tile_finish", "avgpu_tile_res_bytes",
-    "avgpu_set_tile_res_buffers", "avgpu_tile_res_cons", "avgpu_tile_res_settle",
-    "avgpu_last_step_insts", "avgpu_last_kernel_ms", "avgpu_kernel_times", "avgpu_counters", "avgpu_live_objects",
-    "avgpu_state_digests", "avgpu_set_rng_mode", "avgpu_run_serial_updates", "avgpu_set_serial_streams",
-    "avgpu_get_serial_state", "avgpu_set_serial_state", "avgpu_set_timing",
-    "avgpu_get_genotypes", "avgpu_last_genotypes_ms",
-    "avgpu_classify_genotypes", "avgpu_get_arbiter", "avgpu_set_arbiter", "avgpu_reset_arbiter",
-    "avgpu_last_arbiter_ms",
-    "avgpu_get_parent_keys", "avgpu_set_parent_keys",
-    "avgpu_enable_lineage", "avgpu_get_lineage", "avgpu_set_lineage", "avgpu_prune_lineage", "avgpu_last_lineage_ms",
-    "avgpu_landscapes", "avgpu_set_landscape_chunk", "avgpu_last_landscape_ms",
-    "avgpu_landscapes_indel", "avgpu_landscape_pairs",
-    "avgpu_genome_distances", "avgpu_cell_distances", "avgpu_site_histogram", "avgpu_last_distance_ms",
-    "avgpu_kill_cells", "avgpu_kill_prob", "avgpu_kill_rect", "avgpu_kill_genotypes", "avgpu_keep_sample",
-    "avgpu_last_event_ms",
-]
 
 
 # avida.cfg knobs outside avgpu_cfg's implemented set travel in its refused
@@ -531,66 +484,128 @@ def resources_arrays(resources, cells):
     return ra, ca
 
 
-def bind_common(lib, prefix):
-    """Declare argtypes for the functions shared by the product and the oracle."""
-    p = prefix
-    V, I64, I32 = C.c_void_p, C.c_int64, C.c_int32
-    sig = {
-        "load_instset": (C.c_int, [V, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
-        "load_env": (C.c_int, [V, C.c_int, C.POINTER(AvgpuReaction)]),
-        "set_orgs": (C.c_int, [V, I64, I64, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
-                               C.POINTER(C.c_double), C.POINTER(C.c_int32), C.c_int]),
-        "kill": (C.c_int, [V, I64]),
-        "step": (C.c_int, [V, I64, I64, C.POINTER(C.c_int32), I32, C.c_int]),
-        "get_states": (C.c_int, [V, I64, I64, C.POINTER(AvgpuCpuState), C.POINTER(C.c_uint8),
-                                 C.POINTER(C.c_uint8), C.c_int]),
-        "test_genomes": (C.c_int, [V, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
-                                   C.POINTER(AvgpuTestResult), C.c_char_p, C.c_int,
-                                   C.POINTER(C.c_uint8)]),
-        "run_update": (C.c_int, [V, C.POINTER(AvgpuUpdateStats)]),
-        "run_serial_updates": (C.c_int, [V, C.c_int, C.POINTER(AvgpuUpdateStats)]),
-        "run_updates": (C.c_int, [V, C.c_int, C.POINTER(AvgpuUpdateStats)]),
-        "last_step_insts": (C.c_int, [V, C.POINTER(C.c_int64)]),
-        "set_global_totals": (C.c_int, [V, C.c_double, I64]),
-        "destroy": (C.c_int, [V]),
-        # strip tiles (include/avida_gpu.h "strip tiles")
-        "set_tile": (C.c_int, [V, I64, I64]),
-        "tile_buffer_bytes": (C.c_int, [V, C.POINTER(I64), C.POINTER(I64), C.POINTER(I64)]),
-        "set_tile_buffers": (C.c_int, [V] + [V] * 8),
-        "tile_partials": (C.c_int, [V, V]),
-        "tile_begin": (C.c_int, [V, V, C.c_int]),
-        "tile_steps": (C.c_int, [V, V, C.c_int, C.POINTER(C.c_int)]),
-        "tile_begin_step": (C.c_int, [V, V, C.c_int, C.c_int, C.c_int]),
-        "tile_place": (C.c_int, [V, C.c_int, C.c_int]),
-        "tile_finish": (C.c_int, [V, C.POINTER(AvgpuUpdateStats)]),
-        "tile_res_bytes": (C.c_int, [V, C.POINTER(I64)]),
-        "set_tile_res_buffers": (C.c_int, [V] * 5),
-        "tile_res_cons": (C.c_int, [V, V]),
-        "tile_res_settle": (C.c_int, [V, V]),
-        "get_stats": (C.c_int, [V, C.POINTER(AvgpuUpdateStats)]),
-        "load_resources": (C.c_int, [V, C.c_int, C.POINTER(AvgpuResource), C.c_int,
-                                     C.POINTER(AvgpuCellResource)]),
-        "get_resources": (C.c_int, [V, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-        "set_resources": (C.c_int, [V, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
-        "set_states": (C.c_int, [V, I64, I64, C.POINTER(AvgpuCpuState), C.POINTER(C.c_uint8),
-                                 C.POINTER(C.c_uint8), C.c_int]),
-        "set_clock": (C.c_int, [V, C.POINTER(AvgpuUpdateStats)]),
-        "get_census": (C.c_int, [V, I64, I64, V]),
-        "set_genotype_keys": (C.c_int, [V, I64, I64, V]),
-        "get_parent_keys": (C.c_int, [V, I64, I64, V]),   # the product only (the oracle keeps no ancestry)
-        "set_parent_keys": (C.c_int, [V, I64, I64, V]),
-        "state_digests": (C.c_int, [V, I64, I64, V]),
-        "set_rng_mode": (C.c_int, [V, C.c_int, V, I64, V]),
-        "set_serial_streams": (C.c_int, [V, V, I64, V, I64]),
-        "get_serial_state": (C.c_int, [V, C.POINTER(AvgpuSerialState), V, V, V, V, I64]),
-        "set_serial_state": (C.c_int, [V, C.POINTER(AvgpuSerialState), V, V, V, V]),
-    }
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, p + name, None)
+def pack_genomes(genomes):
+    """(uint8 buffer, int32 lens): genomes (op-code byte strings) back to back
+    as the C-ABI takes them; the buffer is never empty"""
+    blob = b"".join(bytes(g) for g in genomes)
+    return ((C.c_uint8 * max(1, len(blob))).from_buffer_copy(blob or b"\0"),
+            (C.c_int32 * len(genomes))(*[len(g) for g in genomes]))
+
+
+V, I, I32, I64, U64, D = C.c_void_p, C.c_int, C.c_int32, C.c_int64, C.c_uint64, C.c_double
+U8P, I32P, I64P, DP = C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+CFGP, STATSP, SERIALP = C.POINTER(AvgpuCfg), C.POINTER(AvgpuUpdateStats), C.POINTER(AvgpuSerialState)
+STATEP = C.POINTER(AvgpuCpuState)
+# Every function of include/avida_gpu.h (tests/test_capi.py holds the two
+# together): name without its prefix -> (restype, argtypes, does the oracle
+# have it as orc_<name>?)
+SIGNATURES = {
+    "last_error": (C.c_char_p, [], True),
+    "cfg_defaults": (None, [CFGP], False),
+    "create": (V, [CFGP, I, I64], False),        # (orc_create takes no device: tests/oracle_lib.py)
+    "check_cfg": (I, [CFGP], False),
+    "destroy": (I, [V], True),
+    "sync": (I, [V], False),
+    "load_instset": (I, [V, I, U8P, I32P], True),
+    "load_env": (I, [V, I, C.POINTER(AvgpuReaction)], True),
+    "load_resources": (I, [V, I, C.POINTER(AvgpuResource), I, C.POINTER(AvgpuCellResource)], True),
+    "set_resources": (I, [V, DP, DP], True),
+    "get_resources": (I, [V, DP, DP], True),
+    "set_org": (I, [V, I64, U8P, I, D, I32P], False),
+    "set_orgs": (I, [V, I64, I64, U8P, I32P, DP, I32P, I], True),
+    "kill": (I, [V, I64], True),
+    "step": (I, [V, I64, I64, I32P, I32, I], True),
+    "run_update": (I, [V, STATSP], True),
+    "run_updates": (I, [V, I, STATSP], True),
+    "run_serial_updates": (I, [V, I, STATSP], True),
+    "set_serial_streams": (I, [V, V, I64, V, I64], True),
+    "get_serial_state": (I, [V, SERIALP, V, V, V, V, I64], True),
+    "set_serial_state": (I, [V, SERIALP, V, V, V, V], True),
+    "update_totals": (I, [V, V], False),
+    "update_run": (I, [V, V, STATSP], False),
+    "set_stream": (I, [V, V], False),
+    "set_rng_mode": (I, [V, I, V, I64, V], True),
+    "get_states": (I, [V, I64, I64, STATEP, U8P, U8P, I], True),
+    "set_states": (I, [V, I64, I64, STATEP, U8P, U8P, I], True),
+    "set_clock": (I, [V, STATSP], True),
+    "get_census": (I, [V, I64, I64, V], True),
+    "set_genotype_keys": (I, [V, I64, I64, V], True),
+    "state_digests": (I, [V, I64, I64, V], True),
+    "test_genomes": (I, [V, I, U8P, I32P, C.POINTER(AvgpuTestResult), C.c_char_p, I, U8P], True),
+    "get_stats": (I, [V, STATSP], True),
+    "stats_vector": (I, [V, C.POINTER(V)], False),
+    "set_global_totals": (I, [V, D, I64], True),
+    "last_step_insts": (I, [V, I64P], True),
+    "last_kernel_ms": (I, [V, DP, I64P], False),
+    "kernel_times": (I, [V, DP, I64P], False),
+    "set_timing": (I, [V, I], False),
+    "counters": (I, [V, I, I64P, I], False),
+    "live_objects": (I64, [], False),
+    # strip tiles (include/avida_gpu.h "strip tiles")
+    "set_tile": (I, [V, I64, I64], True),
+    "tile_buffer_bytes": (I, [V, I64P, I64P, I64P], True),
+    "set_tile_buffers": (I, [V] * 9, True),
+    "tile_partials": (I, [V, V], True),
+    "tile_begin": (I, [V, V, I], True),
+    "tile_steps": (I, [V, V, I, C.POINTER(I)], True),
+    "tile_begin_step": (I, [V, V, I, I, I], True),
+    "tile_place": (I, [V, I, I], True),
+    "tile_finish": (I, [V, STATSP], True),
+    "tile_res_bytes": (I, [V, I64P], True),
+    "set_tile_res_buffers": (I, [V] * 5, True),
+    "tile_res_cons": (I, [V, V], True),
+    "tile_res_settle": (I, [V, V], True),
+    # the genotype table, the device-resident arbiter, ancestry and the lineage
+    # store (DESIGN.md 10): the oracle has the census
+    "get_genotypes": (I, [V, V, I64, C.POINTER(GENOTYPE_TOTALS)], False),
+    "last_genotypes_ms": (I, [V, DP, I64P], False),
+    "classify_genotypes": (I, [V, I64, I32, V], False),
+    "get_arbiter": (I, [V, V, V, I64, V, V], False),
+    "set_arbiter": (I, [V, I64, V, V, V], False),
+    "reset_arbiter": (I, [V], False),
+    "last_arbiter_ms": (I, [V, DP, I64P], False),
+    "get_parent_keys": (I, [V, I64, I64, V], False),
+    "set_parent_keys": (I, [V, I64, I64, V], False),
+    "enable_lineage": (I, [V, I, I64, I64], False),
+    "get_lineage": (I, [V, V, I64, V, I64, V], False),
+    "set_lineage": (I, [V, I64, V, V, I64, V], False),
+    "prune_lineage": (I, [V, V], False),
+    "last_lineage_ms": (I, [V, DP, DP], False),
+    # mutational landscapes, genetic distances, population events: the oracle
+    # runs the specifications of landscape.py, distance.py and popevents.py
+    "landscapes": (I, [V, I, U8P, I32P, I, V, I32P, DP], False),
+    "landscapes_indel": (I, [V, I, U8P, I32P, I, V, I32P], False),
+    "landscape_pairs": (I, [V, I, U8P, I32P, V, V, DP], False),
+    "set_landscape_chunk": (I, [V, I64], False),
+    "last_landscape_ms": (I, [V, DP, I64P, I64P], False),
+    "genome_distances": (I, [V, I, U8P, I32P, I64, I32P, I32P, I32P, I32P], False),
+    "cell_distances": (I, [V, I64, I64, U8P, I32, I32P, I32P], False),
+    "site_histogram": (I, [V, I64, I64, I32P, I64P], False),
+    "last_distance_ms": (I, [V, DP, I64P, I64P], False),
+    "kill_cells": (I, [V, V, I64, I64P], False),
+    "kill_prob": (I, [V, D, U64, I64P], False),
+    "kill_rect": (I, [V, I, I, I, I, I64P], False),
+    "kill_genotypes": (I, [V, V, I64, D, U64, I64P], False),
+    "keep_sample": (I, [V, I64, U64, I64P], False),
+    "last_event_ms": (I, [V, DP, I64P], False),
+}
+EXPORTED = ["avgpu_" + name for name in SIGNATURES]
+
+
+def bind(lib, prefix, signatures, strict=False):
+    """Declare restype and argtypes of {prefix}{name} for every entry of
+    `signatures`.  A symbol the library lacks is an error when `strict`, else
+    it is skipped (the oracle, an older diagnostic build)."""
+    for name, (res, args, *_) in signatures.items():
+        fn = getattr(lib, prefix + name) if strict else getattr(lib, prefix + name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, args
-    getattr(lib, p + "last_error").restype = C.c_char_p
     return lib
+
+
+def bind_common(lib, prefix):
+    """Declare the functions shared by the product and the oracle."""
+    return bind(lib, prefix, {n: s for n, s in SIGNATURES.items() if s[2]})
 
 
 _lib = None
@@ -606,116 +621,29 @@ def lib_build_hash(path=None):
 
 def load_product(path=None):
     """Load the in-tree HIP library; raise if it is missing (no fallback).
-    `path` selects a diagnostic build (tools/phase_clocks.py); it is not cached."""
+    `path` selects a diagnostic build (tools/phase_clocks.py); it is not
+    cached, and like one named by AVGPU_DIAG_LIB it may be an earlier build
+    without the newer functions (tools/gpu/ab_var.sh measures such builds)."""
     global _lib
     if path is None and _lib is not None:
         return _lib
     p = path or os.environ.get("AVGPU_DIAG_LIB") or LIB_PATH   # diagnostic builds (tools/)
     if not os.path.exists(p):
         raise RuntimeError(f"{p} missing: run __graft_entry__.build() first")
-    lib = C.CDLL(p)
-    bind_common(lib, "avgpu_")
-    lib.avgpu_create.restype = C.c_void_p
-    lib.avgpu_create.argtypes = [C.POINTER(AvgpuCfg), C.c_int, C.c_int64]
-    lib.avgpu_cfg_defaults.argtypes = [C.POINTER(AvgpuCfg)]
-    lib.avgpu_check_cfg.argtypes = [C.POINTER(AvgpuCfg)]
-    lib.avgpu_sync.argtypes = [C.c_void_p]
-    lib.avgpu_get_stats.argtypes = [C.c_void_p, C.POINTER(AvgpuUpdateStats)]
-    lib.avgpu_stats_vector.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    lib.avgpu_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double),
-                                         C.POINTER(C.c_int64)]
-    lib.avgpu_kernel_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    lib.avgpu_set_timing.argtypes = [C.c_void_p, C.c_int]
-    lib.avgpu_counters.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.c_int]
-    if p == LIB_PATH or hasattr(lib, "avgpu_live_objects"):   # (as the arbiter below: an earlier diagnostic build)
-        lib.avgpu_live_objects.restype = C.c_int64
-        lib.avgpu_live_objects.argtypes = []
-    lib.avgpu_update_totals.argtypes = [C.c_void_p, C.c_void_p]
-    lib.avgpu_update_run.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(AvgpuUpdateStats)]
-    lib.avgpu_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-    # the genotype table: the product only (the oracle has the census)
-    lib.avgpu_get_genotypes.restype = C.c_int
-    lib.avgpu_get_genotypes.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GENOTYPE_TOTALS)]
-    lib.avgpu_last_genotypes_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    # the device-resident genotype arbiter (a diagnostic library may be an
-    # earlier build without it: tools/gpu/ab_var.sh measures such builds)
-    if p == LIB_PATH or hasattr(lib, "avgpu_classify_genotypes"):
-        lib.avgpu_classify_genotypes.restype = C.c_int
-        lib.avgpu_classify_genotypes.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-        lib.avgpu_get_arbiter.restype = C.c_int
-        lib.avgpu_get_arbiter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
-        lib.avgpu_set_arbiter.restype = C.c_int
-        lib.avgpu_set_arbiter.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.avgpu_reset_arbiter.restype = C.c_int
-        lib.avgpu_reset_arbiter.argtypes = [C.c_void_p]
-        lib.avgpu_last_arbiter_ms.restype = C.c_int
-        lib.avgpu_last_arbiter_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    if p == LIB_PATH or hasattr(lib, "avgpu_enable_lineage"):   # the lineage store (DESIGN.md 10.6)
-        V, I64 = C.c_void_p, C.c_int64
-        lib.avgpu_enable_lineage.restype = C.c_int
-        lib.avgpu_enable_lineage.argtypes = [V, C.c_int, I64, I64]
-        lib.avgpu_get_lineage.restype = C.c_int
-        lib.avgpu_get_lineage.argtypes = [V, V, I64, V, I64, V]
-        lib.avgpu_set_lineage.restype = C.c_int
-        lib.avgpu_set_lineage.argtypes = [V, I64, V, V, I64, V]
-        lib.avgpu_prune_lineage.restype = C.c_int
-        lib.avgpu_prune_lineage.argtypes = [V, V]
-        lib.avgpu_last_lineage_ms.restype = C.c_int
-        lib.avgpu_last_lineage_ms.argtypes = [V, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    # mutational landscapes: the product only (the oracle runs avida_amd.landscape.spec)
-    lib.avgpu_landscapes.restype = C.c_int
-    lib.avgpu_landscapes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int,
-                                     C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double)]
-    lib.avgpu_landscapes_indel.restype = C.c_int
-    lib.avgpu_landscapes_indel.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.c_int,
-                                           C.c_void_p, C.POINTER(C.c_int32)]
-    lib.avgpu_landscape_pairs.restype = C.c_int
-    lib.avgpu_landscape_pairs.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_int32),
-                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
-    lib.avgpu_set_landscape_chunk.restype = C.c_int
-    lib.avgpu_set_landscape_chunk.argtypes = [C.c_void_p, C.c_int64]
-    lib.avgpu_last_landscape_ms.restype = C.c_int
-    lib.avgpu_last_landscape_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
-                                            C.POINTER(C.c_int64)]
-    # genetic distances and the consensus histogram: the product only (the
-    # oracle runs avida_amd.distance's specification); a diagnostic library may
-    # be an earlier build without them
-    if p == LIB_PATH or hasattr(lib, "avgpu_genome_distances"):
-        I32P = C.POINTER(C.c_int32)
-        lib.avgpu_genome_distances.restype = C.c_int
-        lib.avgpu_genome_distances.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint8), I32P, C.c_int64,
-                                               I32P, I32P, I32P, I32P]
-        lib.avgpu_cell_distances.restype = C.c_int
-        lib.avgpu_cell_distances.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.POINTER(C.c_uint8), C.c_int32,
-                                             I32P, I32P]
-        lib.avgpu_site_histogram.restype = C.c_int
-        lib.avgpu_site_histogram.argtypes = [C.c_void_p, C.c_int64, C.c_int64, I32P, C.POINTER(C.c_int64)]
-        lib.avgpu_last_distance_ms.restype = C.c_int
-        lib.avgpu_last_distance_ms.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int64),
-                                               C.POINTER(C.c_int64)]
-    # population events (avida_amd/popevents.py): the product only; a diagnostic
-    # library may be an earlier build without them
-    if p == LIB_PATH or hasattr(lib, "avgpu_kill_cells"):
-        V, I64, U64, I64P = C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(C.c_int64)
-        lib.avgpu_kill_cells.restype = C.c_int
-        lib.avgpu_kill_cells.argtypes = [V, V, I64, I64P]
-        lib.avgpu_kill_prob.restype = C.c_int
-        lib.avgpu_kill_prob.argtypes = [V, C.c_double, U64, I64P]
-        lib.avgpu_kill_rect.restype = C.c_int
-        lib.avgpu_kill_rect.argtypes = [V, C.c_int, C.c_int, C.c_int, C.c_int, I64P]
-        lib.avgpu_kill_genotypes.restype = C.c_int
-        lib.avgpu_kill_genotypes.argtypes = [V, V, I64, C.c_double, U64, I64P]
-        lib.avgpu_keep_sample.restype = C.c_int
-        lib.avgpu_keep_sample.argtypes = [V, I64, U64, I64P]
-        lib.avgpu_last_event_ms.restype = C.c_int
-        lib.avgpu_last_event_ms.argtypes = [V, C.POINTER(C.c_double), I64P]
+    lib = bind(C.CDLL(p), "avgpu_", SIGNATURES, strict=p == LIB_PATH)
     if path is None:
         _lib = lib
     return lib
 
 
-def check(lib, rc, prefix="avgpu_"):
-    if rc < 0:
+def check(lib, rc, prefix="avgpu_", name="call failed"):
+    """the one failure path: rc < 0 raises with the library's last_error"""
+    if rc is not None and rc < 0:
         msg = getattr(lib, prefix + "last_error")()
-        raise RuntimeError(f"{prefix}call failed ({rc}): {msg.decode() if msg else ''}")
+        raise RuntimeError(f"{prefix}{name} ({rc}): {msg.decode() if msg else ''}")
     return rc
+
+
+def call(lib, prefix, name, *args):
+    """{prefix}{name}(*args) through check"""
+    return check(lib, getattr(lib, prefix + name)(*args), prefix, name)

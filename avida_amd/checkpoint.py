@@ -47,31 +47,23 @@ VERSION = 4
 _AGE_OFF = capi.AvgpuCpuState.age.offset
 
 
-def _call(lib, prefix, name, *args):
-    rc = getattr(lib, prefix + name)(*args)
-    if rc is not None and rc < 0:
-        msg = getattr(lib, prefix + "last_error")()
-        raise RuntimeError(f"{prefix}{name}: {msg.decode() if msg else rc}")
-    return rc
-
-
 def save(lib, prefix, handle, ncells, nres, path):
     """Write the world behind `handle` (ncells cells, nres resources) to `path`."""
     st = (capi.AvgpuCpuState * ncells)()
-    _call(lib, prefix, "get_states", handle, 0, ncells, st, None, None, 0)
+    capi.call(lib, prefix, "get_states", handle, 0, ncells, st, None, None, 0)
     cap = max([1] + [st[i].mem_size for i in range(ncells)])
     ops = (C.c_uint8 * (ncells * cap))()
     fl = (C.c_uint8 * (ncells * cap))()
-    _call(lib, prefix, "get_states", handle, 0, ncells, st, ops, fl, cap)
+    capi.call(lib, prefix, "get_states", handle, 0, ncells, st, ops, fl, cap)
     o = np.frombuffer(ops, dtype=np.uint8)
     f = np.frombuffer(fl, dtype=np.uint8)
     tape = (o & 0x3F) | ((f & 0x01) << 6) | (((f >> 2) & 0x01) << 7)
     stats = capi.AvgpuUpdateStats()
-    _call(lib, prefix, "get_stats", handle, C.byref(stats))
+    capi.call(lib, prefix, "get_stats", handle, C.byref(stats))
     levels = np.zeros(max(1, nres))
     grids = np.zeros(max(1, nres * ncells))
     if nres:
-        _call(lib, prefix, "get_resources", handle, levels.ctypes.data_as(C.POINTER(C.c_double)),
+        capi.call(lib, prefix, "get_resources", handle, levels.ctypes.data_as(C.POINTER(C.c_double)),
               grids.ctypes.data_as(C.POINTER(C.c_double)))
     gkeys = capi.get_census(lib, prefix, handle, 0, ncells)["genotype_key"]
     ser = capi.AvgpuSerialState()
@@ -79,13 +71,13 @@ def save(lib, prefix, handle, ncells, nres, path):
     face = np.zeros(ncells, dtype=np.uint8)
     soup = np.zeros(ncells, dtype=np.int32)
     reaper = np.zeros(2 * ncells + 64, dtype=np.int32)
-    _call(lib, prefix, "get_serial_state", handle, C.byref(ser), spec.ctypes.data_as(C.c_void_p),
+    capi.call(lib, prefix, "get_serial_state", handle, C.byref(ser), spec.ctypes.data_as(C.c_void_p),
           face.ctypes.data_as(C.c_void_p), soup.ctypes.data_as(C.c_void_p), reaper.ctypes.data_as(C.c_void_p),
           len(reaper))
     extra = {}
     if prefix == "avgpu_" and hasattr(lib, "avgpu_get_parent_keys"):
         pk = np.zeros(ncells, dtype=np.uint64)
-        _call(lib, prefix, "get_parent_keys", handle, 0, ncells, pk.ctypes.data_as(C.c_void_p))
+        capi.call(lib, prefix, "get_parent_keys", handle, 0, ncells, pk.ctypes.data_as(C.c_void_p))
         extra["pkeys"] = pk
     if prefix == "avgpu_" and hasattr(lib, "avgpu_get_arbiter"):
         # the device-resident genotype arbiter's state (a strip tile keeps none)
@@ -140,19 +132,19 @@ def load(lib, prefix, handle, path):
     tape = z["tape"]
     ops = np.ascontiguousarray(tape & 0x3F)
     fl = np.ascontiguousarray(((tape >> 6) & 0x01) | (((tape >> 7) & 0x01) << 2))
-    _call(lib, prefix, "set_states", handle, 0, ncells, st, ops.ctypes.data_as(C.POINTER(C.c_uint8)),
+    capi.call(lib, prefix, "set_states", handle, 0, ncells, st, ops.ctypes.data_as(C.POINTER(C.c_uint8)),
           fl.ctypes.data_as(C.POINTER(C.c_uint8)), cap)
     if "gkeys" in z.files:                     # genotype keys of the birth genomes
         gk = np.ascontiguousarray(z["gkeys"], dtype=np.uint64)
-        _call(lib, prefix, "set_genotype_keys", handle, 0, ncells, gk.ctypes.data_as(C.c_void_p))
+        capi.call(lib, prefix, "set_genotype_keys", handle, 0, ncells, gk.ctypes.data_as(C.c_void_p))
     if "pkeys" in z.files and prefix == "avgpu_" and hasattr(lib, "avgpu_set_parent_keys"):
         pk = np.ascontiguousarray(z["pkeys"], dtype=np.uint64)   # after set_states, which clears them
-        _call(lib, prefix, "set_parent_keys", handle, 0, ncells, pk.ctypes.data_as(C.c_void_p))
+        capi.call(lib, prefix, "set_parent_keys", handle, 0, ncells, pk.ctypes.data_as(C.c_void_p))
     if "serial" in z.files:                    # the serial world's own state (version >= 4)
         ser = _struct(capi.AvgpuSerialState, z["serial"].tobytes(), "serial state")
         arrs = [np.ascontiguousarray(z[k], dtype=t) for k, t in
                 (("spec", np.int32), ("face", np.uint8), ("soup_perm", np.int32), ("reaper", np.int32))]
-        _call(lib, prefix, "set_serial_state", handle, C.byref(ser), *[a.ctypes.data_as(C.c_void_p) for a in arrs])
+        capi.call(lib, prefix, "set_serial_state", handle, C.byref(ser), *[a.ctypes.data_as(C.c_void_p) for a in arrs])
     if "arb_rows" in z.files and prefix == "avgpu_" and hasattr(lib, "avgpu_set_arbiter"):
         rows = np.frombuffer(z["arb_rows"].tobytes(), dtype=capi.ARBITER_ROW_DTYPE)
         summary = np.frombuffer(z["arb_summary"].tobytes(), dtype=capi.ARBITER_SUMMARY_DTYPE)[0]
@@ -166,10 +158,10 @@ def load(lib, prefix, handle, path):
                 if "the store is off" not in str(e):
                     raise
     stats = _struct(capi.AvgpuUpdateStats, z["stats"].tobytes(), "stats")
-    _call(lib, prefix, "set_clock", handle, C.byref(stats))
+    capi.call(lib, prefix, "set_clock", handle, C.byref(stats))
     levels = np.ascontiguousarray(z["levels"], dtype=np.float64)
     if len(levels):
         grids = np.ascontiguousarray(z["grids"], dtype=np.float64)
-        _call(lib, prefix, "set_resources", handle, levels.ctypes.data_as(C.POINTER(C.c_double)),
+        capi.call(lib, prefix, "set_resources", handle, levels.ctypes.data_as(C.POINTER(C.c_double)),
               grids.ctypes.data_as(C.POINTER(C.c_double)))
     return stats

@@ -221,9 +221,8 @@ def _i32p(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
-def _chk(world, rc, name):
-    if rc < 0:
-        raise RuntimeError(f"{name}: {world.lib.avgpu_last_error().decode()}")
+def _call(world, name, *args):
+    return capi.call(world.lib, "avgpu_", name, world.h, *args)
 
 
 def _edit(a, b):
@@ -239,15 +238,12 @@ def pair_distances(world, genomes, pairs, hamming=True, edit=True, device=None):
         h = np.array([spec_hamming(genomes[i], genomes[j]) for i, j in pairs], dtype=np.int32) if hamming else None
         e = np.array([_edit(genomes[i], genomes[j]) for i, j in pairs], dtype=np.int32) if edit else None
         return h, e
-    blob = b"".join(genomes)
-    buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(blob or b"\0")
-    lens = np.array([len(g) for g in genomes], dtype=np.int32)
+    buf, lens = capi.pack_genomes(genomes)
     pa, pb = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
     h = np.zeros(max(1, len(pairs)), dtype=np.int32) if hamming else None
     e = np.zeros(max(1, len(pairs)), dtype=np.int32) if edit else None
-    _chk(world, world.lib.avgpu_genome_distances(world.h, len(genomes), buf, _i32p(lens), len(pairs), _i32p(pa),
-                                                 _i32p(pb), None if h is None else _i32p(h),
-                                                 None if e is None else _i32p(e)), "avgpu_genome_distances")
+    _call(world, "genome_distances", len(genomes), buf, lens, len(pairs), _i32p(pa), _i32p(pb),
+          None if h is None else _i32p(h), None if e is None else _i32p(e))
     return (None if h is None else h[:len(pairs)]), (None if e is None else e[:len(pairs)])
 
 
@@ -286,11 +282,11 @@ def cell_distances(world, ref, first=0, count=None, hamming=True, edit=True, dev
                 if edit:
                     e[i] = memo[g][1]
         return h, e
-    buf = (C.c_uint8 * max(1, len(ref))).from_buffer_copy(ref or b"\0")
+    buf, _ = capi.pack_genomes([ref])
     h = np.zeros(max(1, count), dtype=np.int32) if hamming else None
     e = np.zeros(max(1, count), dtype=np.int32) if edit else None
-    _chk(world, world.lib.avgpu_cell_distances(world.h, first, count, buf, len(ref), None if h is None else _i32p(h),
-                                               None if e is None else _i32p(e)), "avgpu_cell_distances")
+    _call(world, "cell_distances", first, count, buf, len(ref), None if h is None else _i32p(h),
+          None if e is None else _i32p(e))
     return (None if h is None else h[:count]), (None if e is None else e[:count])
 
 
@@ -304,15 +300,14 @@ def site_histogram(world, first=0, count=None, n_ops=None, device=None):
         return spec_site_histogram(genomes, [len(g) for g in genomes], alive, capi.MAX_INST if n_ops is None else n_ops)
     hist = np.zeros((MAX_GENOME_LENGTH, HIST_COLS), dtype=np.int32)
     living = C.c_int64()
-    _chk(world, world.lib.avgpu_site_histogram(world.h, first, count, _i32p(hist), C.byref(living)),
-         "avgpu_site_histogram")
+    _call(world, "site_histogram", first, count, _i32p(hist), C.byref(living))
     return hist, living.value
 
 
 def last_timing(world):
     """(device ms, pairs, cells) of the last distance or histogram call on the device"""
     ms, p, c = C.c_double(), C.c_int64(), C.c_int64()
-    _chk(world, world.lib.avgpu_last_distance_ms(world.h, C.byref(ms), C.byref(p), C.byref(c)), "avgpu_last_distance_ms")
+    _call(world, "last_distance_ms", C.byref(ms), C.byref(p), C.byref(c))
     return ms.value, p.value, c.value
 
 
@@ -325,12 +320,10 @@ def _test_genomes(world, genomes):
     if getattr(world, "p", None) != "avgpu_":
         return [(r, bytes(child)) for r, _f, child in world.test_genomes(genomes)]
     n = len(genomes)
-    blob = b"".join(genomes)
-    buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
-    lens = (C.c_int32 * n)(*[len(g) for g in genomes])
+    buf, lens = capi.pack_genomes(genomes)
     res = (capi.AvgpuTestResult * n)()
     off = (C.c_uint8 * (n * capi.MAX_GENOME))()
-    _chk(world, world.lib.avgpu_test_genomes(world.h, n, buf, lens, res, None, 0, off), "avgpu_test_genomes")
+    _call(world, "test_genomes", n, buf, lens, res, None, 0, off)
     offb = bytes(off)
     return [(res[i], offb[i * capi.MAX_GENOME:i * capi.MAX_GENOME + res[i].offspring_len]) for i in range(n)]
 

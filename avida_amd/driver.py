@@ -36,77 +36,27 @@ import ctypes as C
 import os
 import sys
 
-from . import capi, checkpoint, datafiles, distance, files, popevents, population, systematics
+from . import capi, datafiles, distance, files, popevents, population, systematics
+from .world import World
 
 
-class ProductWorld:
-    """The world on the GPU through libavida_gpu.so (same methods as the
-    tests' oracle Backend, so the driver runs on either)."""
+class ProductWorld(World):
+    """The world on the GPU through libavida_gpu.so: world.World plus what
+    only the product has (the driver runs on either; a world without these
+    methods takes the host route)."""
 
     def __init__(self, cfg, iset, env, ncells=0, device=0, serial=False):
-        self.lib, self.p = capi.load_product(), "avgpu_"
-        # serial=True: every update under the reference's own schedule
-        # (avgpu_run_serial_updates: per-step merit-weighted picks, births at
-        # once) instead of the batch update
-        self.serial = serial
-        self.h = self.lib.avgpu_create(C.byref(cfg), device, ncells)
-        if not self.h:
-            raise RuntimeError(self.lib.avgpu_last_error().decode())
-        self.cfg = cfg
-        self.ncells = ncells or cfg.world_x * cfg.world_y
-        hid = (C.c_uint8 * len(iset.names))(*iset.handlers)
-        red = (C.c_int32 * len(iset.names))(*iset.redundancy)
-        self._call("load_instset", self.h, len(iset.names), hid, red)
-        self.nres = len(getattr(env, "resources", []))
-        if self.nres:
-            ra, ca = capi.resources_arrays(env.resources, env.cells)
-            self._call("load_resources", self.h, self.nres, ra, len(env.cells), ca)
-        self._call("load_env", self.h, len(env), capi.reactions_array(env))
-
-    def _call(self, name, *args):
-        rc = getattr(self.lib, self.p + name)(*args)
-        if rc is not None and rc < 0:
-            raise RuntimeError(f"{self.p}{name}: {self.lib.avgpu_last_error().decode()}")
-        return rc
-
-    def set_orgs(self, first, genomes, merits=None, deterministic=False):
-        n = len(genomes)
-        blob = b"".join(genomes)
-        buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(blob or b"\0")
-        lens = (C.c_int32 * n)(*[len(g) for g in genomes])
-        m = (C.c_double * n)(*(merits or [0.0] * n))
-        self._call("set_orgs", self.h, first, n, buf, lens, m, None, 1 if deterministic else 0)
+        super().__init__(cfg, iset, env, ncells, device)
+        self.serial = serial       # every update under the reference's own schedule (World.run_update)
 
     def run_update(self):
-        st = capi.AvgpuUpdateStats()
-        if self.serial:
-            self._call("run_serial_updates", self.h, 1, C.byref(st))
-        else:
-            self._call("run_update", self.h, C.byref(st))
-        return st
-
-    def kill(self, cell):
-        self._call("kill", self.h, cell)
-
-    def states(self, first, count, cap=capi.MAX_GENOME):
-        st = (capi.AvgpuCpuState * count)()
-        ops = (C.c_uint8 * (count * cap))()
-        fl = (C.c_uint8 * (count * cap))()
-        self._call("get_states", self.h, first, count, st, ops, fl, cap)
-        return st, bytes(ops), bytes(fl)
+        return super().run_update(self.serial)
 
     def test_genomes(self, genomes, flags_cap=2049):
-        n = len(genomes)
-        blob = b"".join(genomes)
-        buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
-        lens = (C.c_int32 * n)(*[len(g) for g in genomes])
-        res = (capi.AvgpuTestResult * n)()
-        flags = C.create_string_buffer(n * flags_cap)
-        self._call("test_genomes", self.h, n, buf, lens, res, flags, flags_cap, None)
-        return [(res[i], None, None) for i in range(n)]
+        return super().test_genomes(genomes, flags_cap, offspring=False)
 
-    def census(self, first=0, count=None):
-        return capi.get_census(self.lib, self.p, self.h, first, self.ncells - first if count is None else count)
+    def resources(self, spatial=False):
+        return super().resources(False)          # the levels alone: (levels, None)
 
     def parent_keys(self, first=0, count=None):
         """each cell's organism's parent's genotype key, 0 for an injected
@@ -182,22 +132,6 @@ class ProductWorld:
         """a uniform sample of `keep` organisms survives (avgpu_keep_sample;
         SerialTransfer, ApplyBottleneck)"""
         return popevents.apply_keep_sample(self, keep, key)
-
-    def resources(self, spatial=False):
-        lv = (C.c_double * max(1, self.nres))()
-        self._call("get_resources", self.h, lv, None)
-        return list(lv[:self.nres]), None
-
-    def checkpoint(self, path):
-        checkpoint.save(self.lib, self.p, self.h, self.ncells, self.nres, path)
-
-    def restore(self, path):
-        return checkpoint.load(self.lib, self.p, self.h, path)
-
-    def close(self):
-        if self.h:
-            self.lib.avgpu_destroy(self.h)
-            self.h = None
 
 
 def load_config(config_dir):

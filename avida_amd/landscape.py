@@ -406,31 +406,29 @@ def peak_genome(ls, genome, kind=0):
 
 # ---- the device route -------------------------------------------------------
 
+def _call(world, name, *args):
+    return capi.call(world.lib, "avgpu_", name, world.h, *args)
+
+
 def call(world, genomes, distance, chart=None):
     """avgpu_landscapes as it returns: (rows, site_count, chart) -- numpy
     arrays of capi.LANDSCAPE_DTYPE rows, the per-site counts of all genomes
     back to back and (or None) the charts back to back, [site][op] each.
     `world` is a product world (an object with .lib and .h).  chart: None =
     at distance 1 only."""
-    lib, h = world.lib, world.h
     n = len(genomes)
     want_chart = (distance == 1) if chart is None else bool(chart)
-    blob = b"".join(bytes(g) for g in genomes)
-    buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(blob or b"\0")
-    lens = np.array([len(g) for g in genomes], dtype=np.int32)
+    buf, lens = capi.pack_genomes(genomes)
     out = np.zeros(max(1, n), dtype=capi.LANDSCAPE_DTYPE)
-    total = int(lens.sum())
+    total = sum(lens)
     sc = np.zeros(max(1, total), dtype=np.int32)
     ch = None
     if want_chart:
         # the chart's stride is the instruction set's size, which comes back
         # in the rows: room for the largest set
         ch = np.zeros(max(1, total * capi.MAX_INST), dtype=np.float64)
-    rc = lib.avgpu_landscapes(h, n, buf, lens.ctypes.data_as(C.POINTER(C.c_int32)), distance,
-                              out.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.POINTER(C.c_int32)),
-                              ch.ctypes.data_as(C.POINTER(C.c_double)) if ch is not None else None)
-    if rc < 0:
-        raise RuntimeError(f"avgpu_landscapes: {lib.avgpu_last_error().decode()}")
+    _call(world, "landscapes", n, buf, lens, distance, out.ctypes.data_as(C.c_void_p),
+          sc.ctypes.data_as(C.POINTER(C.c_int32)), ch.ctypes.data_as(C.POINTER(C.c_double)) if ch is not None else None)
     if ch is not None:
         ch = ch[:total * int(out[0]["num_insts"])]
     return out[:n], sc[:total], ch
@@ -448,25 +446,16 @@ def full(world, genomes, distance, chart=None):
     return res
 
 
-def _pack(genomes):
-    blob = b"".join(bytes(g) for g in genomes)
-    buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(blob or b"\0")
-    return buf, np.array([len(g) for g in genomes], dtype=np.int32)
-
-
 def call_indel(world, genomes, kind):
     """avgpu_landscapes_indel as it returns: (rows, site_count) -- the counts
     of all genomes back to back, len + 1 each for insertions, len for deletions"""
-    lib, h = world.lib, world.h
     n = len(genomes)
-    buf, lens = _pack(genomes)
+    buf, lens = capi.pack_genomes(genomes)
     out = np.zeros(max(1, n), dtype=capi.LANDSCAPE_DTYPE)
-    total = int(lens.sum()) + (n if kind == INSERT else 0)
+    total = sum(lens) + (n if kind == INSERT else 0)
     sc = np.zeros(max(1, total), dtype=np.int32)
-    rc = lib.avgpu_landscapes_indel(h, n, buf, lens.ctypes.data_as(C.POINTER(C.c_int32)), kind,
-                                    out.ctypes.data_as(C.c_void_p), sc.ctypes.data_as(C.POINTER(C.c_int32)))
-    if rc < 0:
-        raise RuntimeError(f"avgpu_landscapes_indel: {lib.avgpu_last_error().decode()}")
+    _call(world, "landscapes_indel", n, buf, lens, kind, out.ctypes.data_as(C.c_void_p),
+          sc.ctypes.data_as(C.POINTER(C.c_int32)))
     return out[:n], sc[:total]
 
 
@@ -486,18 +475,14 @@ def call_pairs(world, genomes, chart=True):
     """avgpu_landscape_pairs as it returns: (rows, epistasis rows, chart) --
     capi.LANDSCAPE_DTYPE, capi.EPISTASIS_DTYPE and (or None) the one-step
     charts back to back, [site][op] each"""
-    lib, h = world.lib, world.h
     n = len(genomes)
-    buf, lens = _pack(genomes)
+    buf, lens = capi.pack_genomes(genomes)
     out = np.zeros(max(1, n), dtype=capi.LANDSCAPE_DTYPE)
     epi = np.zeros(max(1, n), dtype=capi.EPISTASIS_DTYPE)
-    total = int(lens.sum())
+    total = sum(lens)
     ch = np.zeros(max(1, total * capi.MAX_INST), dtype=np.float64) if chart else None
-    rc = lib.avgpu_landscape_pairs(h, n, buf, lens.ctypes.data_as(C.POINTER(C.c_int32)),
-                                   out.ctypes.data_as(C.c_void_p), epi.ctypes.data_as(C.c_void_p),
-                                   ch.ctypes.data_as(C.POINTER(C.c_double)) if ch is not None else None)
-    if rc < 0:
-        raise RuntimeError(f"avgpu_landscape_pairs: {lib.avgpu_last_error().decode()}")
+    _call(world, "landscape_pairs", n, buf, lens, out.ctypes.data_as(C.c_void_p), epi.ctypes.data_as(C.c_void_p),
+          ch.ctypes.data_as(C.POINTER(C.c_double)) if ch is not None else None)
     if ch is not None:
         ch = ch[:total * int(out[0]["num_insts"])]
     return out[:n], epi[:n], ch
@@ -529,8 +514,10 @@ def full_pairs(world, genomes, chart=True):
 
 def set_chunk(world, cells):
     """avgpu_set_landscape_chunk: cells of the scratch test world"""
-    if world.lib.avgpu_set_landscape_chunk(world.h, cells) < 0:
-        raise ValueError(world.lib.avgpu_last_error().decode())
+    try:
+        _call(world, "set_landscape_chunk", cells)
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
 
 
 def last_timing(world):

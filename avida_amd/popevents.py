@@ -29,6 +29,8 @@ import ctypes as C
 
 import numpy as np
 
+from . import capi
+
 SALT_EVENT = 0x0E7E47D5
 M32 = 0xFFFFFFFF
 
@@ -149,19 +151,11 @@ def on_device(world):
     return getattr(world, "p", None) == "avgpu_" and hasattr(world.lib, "avgpu_kill_cells")
 
 
-def _chk(world, rc, name):
-    if rc < 0:
-        raise RuntimeError(f"{name}: {world.lib.avgpu_last_error().decode()}")
-
-
 def world_seed(world):
     """the seed the world's statistics report (avgpu_update_stats.seed): the
     one the device draws with, on either backend"""
-    from . import capi
     st = capi.AvgpuUpdateStats()
-    rc = getattr(world.lib, world.p + "get_stats")(world.h, C.byref(st))
-    if rc < 0:
-        raise RuntimeError(f"{world.p}get_stats failed")
+    capi.call(world.lib, world.p, "get_stats", world.h, C.byref(st))
     return int(st.seed) or int(world.cfg.seed)      # (a world that has run no update reports 0: the configured seed)
 
 
@@ -188,35 +182,34 @@ def kill_cells(world, cells, device=None):
         victims = np.unique(cells)
         return _kill_each(world, victims[alive[victims]])
     killed = C.c_int64()
-    _chk(world, world.lib.avgpu_kill_cells(world.h, cells.ctypes.data_as(C.c_void_p), len(cells), C.byref(killed)),
-         "avgpu_kill_cells")
+    capi.call(world.lib, "avgpu_", "kill_cells", world.h, cells.ctypes.data_as(C.c_void_p), len(cells), C.byref(killed))
     return killed.value
 
 
 def _run(world, name, spec, device, *args):
-    """`name`(*args) on the device, else spec(alive, keys) killed cell by cell"""
+    """avgpu_`name`(*args) on the device, else spec(alive, keys) killed cell by cell"""
     if not (on_device(world) if device is None else device):
         alive, gkeys = alive_mask(world)
         return _kill_each(world, spec(alive, gkeys))
     killed = C.c_int64()
-    _chk(world, getattr(world.lib, name)(world.h, *args, C.byref(killed)), name)
+    capi.call(world.lib, "avgpu_", name, world.h, *args, C.byref(killed))
     return killed.value
 
 
 def apply_kill_prob(world, p, key, device=None):
-    return _run(world, "avgpu_kill_prob", lambda a, g: kill_prob(a, world_seed(world), key, p), device,
+    return _run(world, "kill_prob", lambda a, g: kill_prob(a, world_seed(world), key, p), device,
                 C.c_double(_check_p(p)), C.c_uint64(key))
 
 
 def apply_kill_rect(world, x1=0, y1=0, x2=0, y2=0, device=None):
     wx, wy = world.cfg.world_x, world.cfg.world_y
-    return _run(world, "avgpu_kill_rect", lambda a, g: kill_rect(a, wx, wy, x1, y1, x2, y2), device,
+    return _run(world, "kill_rect", lambda a, g: kill_rect(a, wx, wy, x1, y1, x2, y2), device,
                 int(x1), int(y1), int(x2), int(y2))
 
 
 def apply_kill_genotypes(world, keys, p, key, device=None):
     keys = np.ascontiguousarray(list(keys), dtype=np.uint64)
-    return _run(world, "avgpu_kill_genotypes",
+    return _run(world, "kill_genotypes",
                 lambda a, g: kill_genotypes(a, g, world_seed(world), key, keys, p), device,
                 keys.ctypes.data_as(C.c_void_p), len(keys), C.c_double(_check_p(p)), C.c_uint64(key))
 
@@ -224,14 +217,14 @@ def apply_kill_genotypes(world, keys, p, key, device=None):
 def apply_keep_sample(world, keep, key, device=None):
     if keep < 0:
         raise ValueError("keep < 0")
-    return _run(world, "avgpu_keep_sample", lambda a, g: keep_sample(a, world_seed(world), key, keep), device,
+    return _run(world, "keep_sample", lambda a, g: keep_sample(a, world_seed(world), key, keep), device,
                 C.c_int64(keep), C.c_uint64(key))
 
 
 def last_timing(world):
     """(device ms, control words read) of the last event call on the device"""
     ms, cells = C.c_double(), C.c_int64()
-    _chk(world, world.lib.avgpu_last_event_ms(world.h, C.byref(ms), C.byref(cells)), "avgpu_last_event_ms")
+    capi.call(world.lib, "avgpu_", "last_event_ms", world.h, C.byref(ms), C.byref(cells))
     return ms.value, cells.value
 
 
@@ -245,7 +238,7 @@ def dead_genotype_keys(world, iset, cap=None):
     population.save_population obtains it: the birth_length-site prefix of a
     member's memory that still hashes to the key; a genotype all of whose
     members have copied into their own first sites has none."""
-    from . import capi, systematics
+    from . import systematics
     cap = cap or capi.MAX_GENOME
     alive, gkeys = alive_mask(world)
     st, ops, _ = world.states(0, len(alive), cap)

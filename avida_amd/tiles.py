@@ -29,12 +29,7 @@ import ctypes as C
 
 import torch
 
-
-def _check(lib, prefix, rc, what):
-    if rc is not None and rc < 0:
-        msg = getattr(lib, prefix + "last_error")()
-        raise RuntimeError(f"{prefix}{what} failed ({rc}): {msg.decode() if msg else ''}")
-    return rc
+from . import capi
 
 
 class Tile:
@@ -45,10 +40,9 @@ class Tile:
         self.lib, self.p, self.h = lib, prefix, handle
         self.row0 = row0
         self.ntiles = ntiles
-        _check(lib, prefix, getattr(lib, prefix + "set_tile")(handle, row0, arena_bytes), "set_tile")
+        self.call("set_tile", row0, arena_bytes)
         pb, hb, rb = C.c_int64(), C.c_int64(), C.c_int64()
-        _check(lib, prefix, getattr(lib, prefix + "tile_buffer_bytes")(
-            handle, C.byref(pb), C.byref(hb), C.byref(rb)), "tile_buffer_bytes")
+        self.call("tile_buffer_bytes", C.byref(pb), C.byref(hb), C.byref(rb))
         self.n_part = pb.value // 8
         u8 = dict(dtype=torch.uint8, device=device)
         self.part = torch.zeros(self.n_part, dtype=torch.float64, device=device)
@@ -59,26 +53,23 @@ class Tile:
         self.rec_recv = [torch.zeros(rb.value, **u8) for _ in range(2)]
         ptrs = [C.c_void_p(t.data_ptr()) for t in
                 self.halo_send + self.halo_recv + self.rec_send + self.rec_recv]
-        _check(lib, prefix, getattr(lib, prefix + "set_tile_buffers")(handle, *ptrs),
-               "set_tile_buffers")
+        self.call("set_tile_buffers", *ptrs)
         self.resources_changed(device)
 
     def resources_changed(self, device):
         """(Re)size the resource edge-row buffers after avgpu_load_resources."""
-        lib, prefix, handle = self.lib, self.p, self.h
         sb = C.c_int64()
-        _check(lib, prefix, getattr(lib, prefix + "tile_res_bytes")(handle, C.byref(sb)), "tile_res_bytes")
+        self.call("tile_res_bytes", C.byref(sb))
         f64 = dict(dtype=torch.float64, device=device)
         self.res_send = [torch.zeros(max(1, sb.value // 8), **f64) for _ in range(2)]
         self.res_recv = [torch.zeros(max(1, sb.value // 8), **f64) for _ in range(2)]
         self.has_res_rows = sb.value > 0
         ptrs = [C.c_void_p(t.data_ptr()) for t in self.res_send + self.res_recv]
-        _check(lib, prefix, getattr(lib, prefix + "set_tile_res_buffers")(handle, *ptrs),
-               "set_tile_res_buffers")
+        self.call("set_tile_res_buffers", *ptrs)
         self.cons = torch.zeros(16, dtype=torch.int64, device=device)   # AVGPU_MAX_RESOURCES
 
     def call(self, name, *args):
-        return _check(self.lib, self.p, getattr(self.lib, self.p + name)(self.h, *args), name)
+        return capi.call(self.lib, self.p, name, self.h, *args)
 
 
 def _buffers(kind):

@@ -28,6 +28,7 @@ import ctypes as C
 import os
 
 from avida_amd import capi, files
+from avida_amd.world import World
 
 STACK_SIZE = capi.STACK_SIZE
 
@@ -76,11 +77,11 @@ def trace(lib, handle, first, count, n_instructions, iset, mode=capi.MODE_FROZEN
     ops = (C.c_uint8 * (count * cap))()
     fl = (C.c_uint8 * (count * cap))()
     for _ in range(n_instructions):
-        capi.check(lib, lib.avgpu_get_states(handle, first, count, st, ops, fl, cap))
+        capi.call(lib, "avgpu_", "get_states", handle, first, count, st, ops, fl, cap)
         raw = bytes(ops)
         out.append([status_text(st[i], raw[i * cap:(i + 1) * cap], iset) for i in range(count)])
-        capi.check(lib, lib.avgpu_step(handle, first, count, None, 1, mode))
-    capi.check(lib, lib.avgpu_sync(handle))
+        capi.call(lib, "avgpu_", "step", handle, first, count, None, 1, mode)
+    capi.call(lib, "avgpu_", "sync", handle)
     return out
 
 
@@ -98,26 +99,16 @@ def main():
     cfg = capi.cfg_from_avida(files.read_avida_cfg(None, {"COPY_MUT_PROB": 0.0, "DIVIDE_INS_PROB": 0.0,
                                                           "DIVIDE_DEL_PROB": 0.0}))
     genome = files.read_org(os.path.join(args.config, args.genome), iset)
-    lib = capi.load_product()
-    h = lib.avgpu_create(C.byref(cfg), 0, 1)
-    if not h:
-        raise SystemExit(lib.avgpu_last_error().decode())
-    hid = (C.c_uint8 * len(iset.names))(*iset.handlers)
-    red = (C.c_int32 * len(iset.names))(*iset.redundancy)
-    capi.check(lib, lib.avgpu_load_instset(h, len(iset.names), hid, red))
-    arr = capi.reactions_array(env)
-    capi.check(lib, lib.avgpu_load_env(h, len(env), arr))
-    buf = (C.c_uint8 * len(genome)).from_buffer_copy(genome)
-    lens = (C.c_int32 * 1)(len(genome))
-    capi.check(lib, lib.avgpu_set_orgs(h, 0, 1, buf, lens, None, None, 1))   # test-CPU inputs
-    steps = trace(lib, h, 0, 1, args.n, iset)
+    world = World(cfg, iset, env, ncells=1)
+    world.set_orgs(0, [genome], deterministic=True)   # test-CPU inputs
+    steps = trace(world.lib, world.h, 0, 1, args.n, iset)
     text = "".join(s[0] for s in steps)
     if args.out == "-":
         print(text, end="")
     else:
         with open(args.out, "w") as f:
             f.write(text)
-    lib.avgpu_destroy(h)
+    world.close()
 
 
 if __name__ == "__main__":

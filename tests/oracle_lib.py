@@ -9,6 +9,7 @@ import os
 import subprocess
 
 from avida_amd import capi, files
+from avida_amd.world import World
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -17,6 +18,15 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 _lib = None
 
+# what only the oracle has, or has with a signature of its own
+ORACLE_ONLY = {
+    "create": (C.c_void_p, [C.POINTER(capi.AvgpuCfg), C.c_int64]),
+    "destroy": (None, [C.c_void_p]),
+    "rec_exhausted": (C.c_int64, []),
+    "last_budgets": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "op_hist": (C.c_int, [C.POINTER(C.c_int64), C.c_int]),
+}
+
 
 def load_oracle():
     global _lib
@@ -24,83 +34,35 @@ def load_oracle():
         return _lib
     if not os.path.exists(ORACLE_SO):
         subprocess.run(["make", "-s", "-C", ORACLE_DIR], check=True)
-    lib = C.CDLL(ORACLE_SO)
-    capi.bind_common(lib, "orc_")
-    lib.orc_create.restype = C.c_void_p
-    lib.orc_create.argtypes = [C.POINTER(capi.AvgpuCfg), C.c_int64]
-    lib.orc_destroy.restype = None
-    lib.orc_run_serial_updates.argtypes = [C.c_void_p, C.c_int, C.POINTER(capi.AvgpuUpdateStats)]
-    lib.orc_rec_exhausted.restype = C.c_int64
-    _lib = lib
-    return lib
+    lib = capi.bind_common(C.CDLL(ORACLE_SO), "orc_")
+    _lib = capi.bind(lib, "orc_", ORACLE_ONLY)
+    return _lib
 
 
-class Backend:
-    """Uniform wrapper over the oracle (prefix orc_) and the product (avgpu_)."""
+class Backend(World):
+    """World over the oracle (kind "oracle", prefix orc_) or the product (any
+    other kind, avgpu_), plus what only the tests need."""
 
     def __init__(self, kind, cfg: capi.AvgpuCfg, instset: files.InstSet, reactions, ncells=0,
                  device=0):
-        self.kind = kind
-        if kind == "oracle":
-            self.lib, self.p = load_oracle(), "orc_"
-            self.h = self.lib.orc_create(C.byref(cfg), ncells)
-        else:
-            self.lib, self.p = capi.load_product(), "avgpu_"
-            self.h = self.lib.avgpu_create(C.byref(cfg), device, ncells)
-            if not self.h:
-                raise RuntimeError(self.lib.avgpu_last_error().decode())
-        self.cfg = cfg
-        self.ncells = ncells or cfg.world_x * cfg.world_y
-        self.instset = instset
-        hid = (C.c_uint8 * len(instset.names))(*instset.handlers)
-        red = (C.c_int32 * len(instset.names))(*instset.redundancy)
-        self._call("load_instset", self.h, len(instset.names), hid, red)
-        self.nres = 0
-        if getattr(reactions, "resources", None):   # resources first: reactions name them
-            self.load_resources(reactions)
-        arr = capi.reactions_array(reactions)
-        self._call("load_env", self.h, len(reactions), arr)
-
-    def _call(self, name, *args):
-        rc = getattr(self.lib, self.p + name)(*args)
-        if rc is not None and rc < 0:
-            msg = getattr(self.lib, self.p + "last_error")()
-            raise RuntimeError(f"{self.p}{name}: {msg.decode() if msg else rc}")
-        return rc
-
-    def close(self):
-        if self.h:
-            getattr(self.lib, self.p + "destroy")(self.h)
-            self.h = None
+        self.kind, self.instset = kind, instset
+        super().__init__(cfg, instset, reactions, ncells, device, oracle=load_oracle() if kind == "oracle" else None)
 
     def set_orgs(self, first, genomes, merits=None, inputs=None, deterministic=True):
-        n = len(genomes)
-        blob = b"".join(genomes)
-        buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(blob or b"\0")
-        lens = (C.c_int32 * n)(*[len(g) for g in genomes])
-        m = (C.c_double * n)(*(merits or [0.0] * n))
-        inp = None
-        if inputs is not None:
-            flat = [v for t in inputs for v in t]
-            inp = (C.c_int32 * len(flat))(*flat)
-        self._call("set_orgs", self.h, first, n, buf, lens, m, inp, 1 if deterministic else 0)
+        super().set_orgs(first, genomes, merits, inputs, deterministic)
 
     def set_orgs_np(self, first, blob, lens, merits=None, deterministic=False):
         """set_orgs for large worlds: genomes packed in `blob` (bytes), lens /
         merits numpy arrays"""
         import numpy as np
         lens = np.ascontiguousarray(lens, dtype=np.int32)
-        n = len(lens)
-        buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(blob or b"\0")
+        buf, _ = capi.pack_genomes([blob])
         m = None
         if merits is not None:
             merits = np.ascontiguousarray(merits, dtype=np.float64)
             m = merits.ctypes.data_as(C.POINTER(C.c_double))
-        self._call("set_orgs", self.h, first, n, buf, lens.ctypes.data_as(C.POINTER(C.c_int32)), m, None,
+        self._call("set_orgs", self.h, first, len(lens), buf, lens.ctypes.data_as(C.POINTER(C.c_int32)), m, None,
                    1 if deterministic else 0)
-
-    def kill(self, cell):
-        self._call("kill", self.h, cell)
 
     def step(self, first, count, budget=None, uniform=0, mode=capi.MODE_FROZEN):
         b = None
@@ -109,13 +71,6 @@ class Backend:
         self._call("step", self.h, first, count, b, uniform, mode)
         if self.kind != "oracle":
             self.lib.avgpu_sync(self.h)
-
-    def states(self, first, count, cap=capi.MAX_GENOME):
-        st = (capi.AvgpuCpuState * count)()
-        ops = (C.c_uint8 * (count * cap))()
-        fl = (C.c_uint8 * (count * cap))()
-        self._call("get_states", self.h, first, count, st, ops, fl, cap)
-        return st, bytes(ops), bytes(fl)
 
     def digests(self, first=0, count=None):
         """per-cell state digests (numpy uint64) of a cell range:
@@ -147,64 +102,9 @@ class Backend:
         self._call("counters", self.h, cumulative, out, capi.NUM_COUNTERS)
         return list(out)
 
-    def census(self, first=0, count=None):
-        """avgpu_census rows (numpy, capi.CENSUS_DTYPE) of a cell range"""
-        if count is None:
-            count = self.ncells - first
-        return capi.get_census(self.lib, self.p, self.h, first, count)
-
-    def test_genomes(self, genomes, flags_cap=2049):
-        n = len(genomes)
-        blob = b"".join(genomes)
-        buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
-        lens = (C.c_int32 * n)(*[len(g) for g in genomes])
-        res = (capi.AvgpuTestResult * n)()
-        flags = C.create_string_buffer(n * flags_cap)
-        off = (C.c_uint8 * (n * capi.MAX_GENOME))()
-        self._call("test_genomes", self.h, n, buf, lens, res, flags, flags_cap, off)
-        out = []
-        raw = flags.raw
-        offb = bytes(off)
-        for i in range(n):
-            r = res[i]
-            f = raw[i * flags_cap:(i + 1) * flags_cap].split(b"\0", 1)[0].decode()
-            child = offb[i * capi.MAX_GENOME:i * capi.MAX_GENOME + r.offspring_len]
-            out.append((r, f, child))
-        return out
-
-    def load_resources(self, env):
-        self.nres = len(env.resources)
-        ra, ca = capi.resources_arrays(env.resources, env.cells)
-        self._call("load_resources", self.h, len(env.resources), ra, len(env.cells), ca)
-
-    def resources(self, spatial=False):
-        """(levels, per-cell grids or None): avgpu_get_resources"""
-        nres = self.nres
-        n = self.ncells
-        lv = (C.c_double * max(1, nres))()
-        sp = (C.c_double * max(1, nres * n))() if spatial else None
-        self._call("get_resources", self.h, lv, sp)
-        grids = [list(sp[r * n:(r + 1) * n]) for r in range(nres)] if spatial else None
-        return list(lv[:nres]), grids
-
-    def checkpoint(self, path):
-        from avida_amd import checkpoint
-        checkpoint.save(self.lib, self.p, self.h, self.ncells, self.nres, path)
-
-    def restore(self, path):
-        from avida_amd import checkpoint
-        return checkpoint.load(self.lib, self.p, self.h, path)
-
-    def run_update(self):
-        st = capi.AvgpuUpdateStats()
-        self._call("run_update", self.h, C.byref(st))
-        return st
-
     def run_serial_update(self):
         """one update of the serial world (reference schedule, births at once)"""
-        st = capi.AvgpuUpdateStats()
-        self._call("run_serial_updates", self.h, 1, C.byref(st))
-        return st
+        return World.run_update(self, serial=True)     # (not a subclass's run_update, which may call this)
 
 
 def recalculate(backend: Backend, genomes, generations=3):

@@ -13,13 +13,74 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "avida_gpu.h")
 
 
+def _prototypes():
+    """{function: (C return type, [C argument types])} of the header's
+    prototypes, comments stripped and argument names dropped"""
+    txt = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S))
+    out = {}
+    for m in re.finditer(r"\b(avgpu_[a-z_]+)\s*\(([^;{]*?)\)\s*;", txt):
+        ret = " ".join(re.split(r"[;}]", txt[:m.start()])[-1].split()).replace(" *", "*")
+        args = [" ".join(a.split()) for a in m.group(2).split(",")]
+        args = [] if args == ["void"] else [re.sub(r"\s*\w+$", "", a) if "*" not in a else a[:a.rindex("*") + 1]
+                                            for a in args]
+        assert m.group(1) not in out, m.group(1)
+        out[m.group(1)] = (ret, args)
+    return out
+
+
 def _declared():
-    txt = open(HEADER).read()
-    return sorted(set(re.findall(r"\b(avgpu_[a-z_]+)\s*\(", txt)))
+    return sorted(_prototypes())
 
 
 def test_header_and_mirror_agree():
     assert _declared() == sorted(capi.EXPORTED)
+    assert len(capi.EXPORTED) == len(set(capi.EXPORTED))
+
+
+# the ctypes types that may stand for a C scalar of the header (any pointer: a
+# POINTER(...), c_void_p or c_char_p)
+SCALARS = {"int64_t": (C.c_int64,), "uint64_t": (C.c_uint64,), "double": (C.c_double,),
+           "int": (C.c_int, C.c_int32), "int32_t": (C.c_int, C.c_int32)}
+RETURNS = {"void": None, "const char*": C.c_char_p, "avgpu_world*": C.c_void_p, "int64_t": C.c_int64, "int": C.c_int}
+
+
+def _is_pointer(t):
+    return t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer))
+
+
+def signature_mismatches(signatures):
+    """what of `signatures` (capi.SIGNATURES' layout) disagrees with the
+    header's prototypes: argument counts, each argument's kind, return types"""
+    bad = []
+    for name, (ret, args) in _prototypes().items():
+        res, argtypes = signatures[name[len("avgpu_"):]][:2]
+        if res is not RETURNS[ret]:
+            bad.append((name, "returns", ret, res))
+        if len(argtypes) != len(args):
+            bad.append((name, "arguments", len(args), len(argtypes)))
+            continue
+        for k, (c, t) in enumerate(zip(args, argtypes)):
+            if not (_is_pointer(t) if c.endswith("*") else t in SCALARS[c]):
+                bad.append((name, k, c, t))
+    return bad
+
+
+def test_signature_table_matches_the_prototypes():
+    """Every prototype of include/avida_gpu.h has a capi.SIGNATURES entry with
+    the same number of arguments, each of the header's kind (64-bit integers,
+    doubles, ints, pointers), and the header's return type; no library needed."""
+    assert len(_prototypes()) == len(capi.SIGNATURES) >= 83
+    assert signature_mismatches(capi.SIGNATURES) == []
+
+
+def test_loaded_library_carries_the_table():
+    """capi.load_product declares every function from the table: the loaded
+    library's restype and argtypes are the table's own objects."""
+    build.build()
+    lib = capi.load_product()
+    for name, (res, args, _shared) in capi.SIGNATURES.items():
+        fn = getattr(lib, "avgpu_" + name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
 
 
 def test_library_exports_every_symbol():
